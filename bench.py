@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Benchmark: AdaptSegNet adversarial-train images/sec on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4] [--full] [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  ``--full`` adds what
+takes runs of its own: the roofline (one extra untimed step with events around every conv and
+HBM-bound launch, the dominant conv kernel's events inside the timed steps) and the CPU baseline
+(``--no-roofline`` / ``--no-cpu-baseline`` drop either again).  ``--dump-outputs DIR`` writes what
+the last timed step handed its caller (dump_outputs below) as ``DIR/<name>.npy``.
 
 One "step" = one full adversarial iteration of train_gta2cityscapes_multi.py on the HIP
 engine (2 G forwards, 2 G backwards, D forwards/backwards, SGD + Adam) over one synthetic
@@ -15,14 +21,14 @@ Conv math: the fp32 configs run F32X3 by default (fp32-accurate convs on the bf1
 exact three-term bf16 operand splits, six bf16 products per fp32 product; conv_x3.hpp),
 ``--conv-math f32`` the fp32-input MFMA kernels; c5 runs bf16 operands.
 
-roofline: the dominant implicit-GEMM conv kernel symbol (the most kernel execution time per
+roofline (--full): the dominant implicit-GEMM conv kernel symbol (the most kernel execution time per
 step, from execution-time events of every conv launch of one untimed step) is launched with
 hipExtLaunchKernel start/stop events inside the library during the timed steps, which time the
 kernel's own execution as rocprofv3 does; achieved = its
 algorithmic FLOPs / its summed execution time, against that kernel's MFMA ceiling: the fp32 MFMA
 peak (157.3 TFLOP/s) for the fp32-input kernels, the bf16 dense peak / 6 (419.4 TFLOP/s of
 fp32 products) for F32X3, the bf16 dense peak (2516.6) for bf16.
-cpu_baseline: the oracle (stock-PyTorch CPU restatement of the reference step, the
+cpu_baseline (--full): the oracle (stock-PyTorch CPU restatement of the reference step, the
 reference's own arithmetic) timed on this host for ONE single-level step at batch 1.
 """
 from __future__ import annotations
@@ -308,6 +314,39 @@ def cpu_baseline(threads):
                            "(profiles/r4/cpu_calibration.json)"}
 
 
+DUMP_SAMPLE = 2 * 1024 * 1024   # elements per dumped array (8 MB in float32; six arrays at most)
+
+
+def dump_outputs(outdir, losses, models):
+    """What the last timed step handed its caller, as ``outdir/<name>.npy`` (float32):
+
+    * ``<loss>.npy``: each loss value of the step (StepLosses.values()), shape (1,);
+    * ``<model>_params.npy`` / ``<model>_grads.npy`` for G, D1, D2: the parameters after the step's
+      optimiser update and the gradients it applied, every ``named_parameters()`` entry flattened
+      in its logical (Cout, Cin, kh, kw) order and concatenated (no gradient: zeros).  Past
+      DUMP_SAMPLE elements a fixed, seeded sample of positions (the same for both arrays and for
+      every run) is kept, so the whole dump stays under 64 MB.
+    """
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in losses.items():
+        np.save(os.path.join(outdir, f"{k}.npy"), np.asarray([v], dtype=np.float32))
+    for tag, m in models.items():
+        if m is None:
+            continue
+        ps = [p for _, p in m.named_parameters()]
+        with torch.no_grad():
+            flat_p = torch.cat([p.detach().reshape(-1).float() for p in ps])
+            flat_g = torch.cat([(torch.zeros_like(p) if p.grad is None else p.grad).detach().reshape(-1).float()
+                                for p in ps])
+            n = flat_p.numel()
+            if n > DUMP_SAMPLE:
+                idx = np.sort(np.random.default_rng(1338).choice(n, DUMP_SAMPLE, replace=False))
+                idx = torch.from_numpy(idx).to(flat_p.device)
+                flat_p, flat_g = flat_p[idx], flat_g[idx]
+        np.save(os.path.join(outdir, f"{tag}_params.npy"), flat_p.cpu().numpy())
+        np.save(os.path.join(outdir, f"{tag}_grads.npy"), flat_g.cpu().numpy())
+
+
 def init_distributed(backend, local, init=None, set_device=None):
     """One process per GPU (torch.distributed.run sets RANK / LOCAL_RANK / WORLD_SIZE /
     MASTER_*): bind the local GPU and create the process group.  ``nccl`` (= RCCL over xGMI)
@@ -338,8 +377,14 @@ def main():
     ap.add_argument("--conv-math", default="f32x3", choices=("f32x3", "f32x3_presplit", "f32"),
                     help="conv arithmetic of the fp32 configs: f32x3 (default, fp32-accurate on the "
                          "bf16 MFMA) or f32 (the fp32-input MFMA kernels)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the roofline (one extra untimed step, "
+                         "the dominant conv kernel's events in the timed steps) and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller (losses, "
+                         "parameters, gradients; float32, at most 64 MB) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave the roofline out")
     ap.add_argument("--overlap", default="auto", choices=("auto", "on", "off"),
                     help="run the target-domain pass on a second stream, overlapping the source "
                          "backward (StepConfig.overlap_domains; auto: on for DeeplabMulti)")
@@ -358,6 +403,8 @@ def main():
                     help="process-group backend for N > 1 (nccl = RCCL over xGMI; gloo only to "
                          "rehearse the multi-rank path with several ranks on one GPU)")
     args = ap.parse_args()
+    roofline = args.full and not args.no_roofline
+    cpu_base = args.full and not args.no_cpu_baseline
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -413,10 +460,10 @@ def main():
                          first_head=not scfg.second_head_only)
     step_flops = sum(inv.values())
     # the roofline kernel: the conv symbol with the most measured kernel time per step (below);
-    # without the untimed timing step (--no-roofline) the one with the most algorithmic FLOPs
+    # without the untimed timing step (a plain run, or --no-roofline) the one with the most algorithmic FLOPs
     dom = max(inv, key=inv.get)
     hbm = []
-    if not args.no_roofline:
+    if roofline:
         # HBM-bound kernels (interp / loss / BN passes): hipEvent pairs around each of their
         # ~400 launches per step, over ONE extra untimed step — inside the timed region those
         # event pairs cost ~2 % of the step.  The timed region keeps only the dominant conv
@@ -471,14 +518,14 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    it0 = args.warmup + (0 if args.no_roofline else 1)   # after the HBM-timing step
+    it0 = args.warmup + (1 if roofline else 0)   # after the HBM-timing step
     for i in range(args.steps):
         L = trainer.step(it0 + i, batches)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    if not args.no_roofline:
+    if roofline:
         K.timing_enable(dom, enable=False)
         k_ms, k_flops, k_launches = K.timing_read()
     if world > 1:
@@ -489,6 +536,8 @@ def main():
     for k, v in losses.items():
         if not np.isfinite(v):
             raise RuntimeError(f"non-finite loss {k}={v}")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, losses, {"G": model, "D1": D1, "D2": D2})
 
     ms_per_step = elapsed / args.steps * 1e3
     pairs = batch * world * args.steps
@@ -518,7 +567,7 @@ def main():
                    # activations until D's own step: ADVICE r5; --no-d-reuse is the low-memory arm)
                    "peak_mem_gb": torch.cuda.max_memory_allocated(dev) / 1e9},
     }
-    if not args.no_roofline and k_launches:
+    if roofline and k_launches:
         avg_ms = k_ms / k_launches
         # algorithmic FLOPs from the step inventory (unpadded geometries): the library's own
         # count includes the zero channels of the channel-padded thin convs (D.conv1 runs
@@ -555,7 +604,7 @@ def main():
         # north_star: HBM GB/s of the interp / loss kernels (and the BN passes) vs the peak,
         # live hipEvents over one untimed step right before the timed region
         out["hbm_kernels"] = hbm
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu_base:
         try:
             aff = len(os.sched_getaffinity(0))
         except AttributeError:  # pragma: no cover

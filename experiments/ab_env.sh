@@ -12,7 +12,7 @@ for r in $(seq 1 "${ROUNDS:-2}"); do
       out=gpurun_out/ab/${name}_${cfg}_${r}.json
       # shellcheck disable=SC2086
       env $envs timeout -k 10 300 python -u bench.py --config "$cfg" --steps "${STEPS:-10}" --warmup 3 \
-        --no-cpu-baseline $args > "$out" 2> "${out%.json}.err" || { tail -5 "${out%.json}.err"; exit 3; }
+        --full --no-cpu-baseline $args > "$out" 2> "${out%.json}.err" || { tail -5 "${out%.json}.err"; exit 3; }
       python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); bk={k['selector']: round(k['frac'],3) for k in d['roofline']['by_kernel']}; print('ab', sys.argv[2], sys.argv[3], round(d['value'],3), 'img/s', round(d['ms_per_step'],2), 'ms', bk, flush=True)" "$out" "$cfg" "$name"
     done
   done

@@ -13,8 +13,9 @@ fi
 for CFG in ${CFGS:-c2 c3}; do
 for rep in 1 2; do
 for v in ${ARMS:-0 1 2}; do
-  ADAPTSEG_X3_BWD_TERMS=$v timeout -k 10 300 python -u bench.py --config $CFG --steps 10 --warmup 3 --no-cpu-baseline > gpurun_out/abt.json 2>gpurun_out/abt.err || { tail -5 gpurun_out/abt.err; exit 4; }
-  python -c "import json,sys; d=json.loads(open('gpurun_out/abt.json').read().strip().splitlines()[-1]); bk={k['selector']: round(k['frac'],3) for k in d['roofline']['by_kernel']}; print('bwdterms', sys.argv[1], sys.argv[2], round(d['value'],3), 'img/s', round(d['ms_per_step'],2), 'ms', bk)" "$v" "$CFG"
+  O=${BENCH_OUT:-bench_out}; mkdir -p "$O"
+  ADAPTSEG_X3_BWD_TERMS=$v timeout -k 10 300 python -u bench.py --full --config $CFG --steps 10 --warmup 3 --no-cpu-baseline > "$O/abt.json" 2> "$O/abt.err" || { tail -5 "$O/abt.err"; exit 4; }
+  python -c "import json,sys; d=json.loads(open(sys.argv[3]).read().strip().splitlines()[-1]); bk={k['selector']: round(k['frac'],3) for k in d['roofline']['by_kernel']}; print('bwdterms', sys.argv[1], sys.argv[2], round(d['value'],3), 'img/s', round(d['ms_per_step'],2), 'ms', bk)" "$v" "$CFG" "$O/abt.json"
 done
 done
 done

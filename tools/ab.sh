@@ -23,7 +23,7 @@ for r in $(seq 1 "$ROUNDS"); do
       name=${arm%%=*}; args=${arm#*=}
       out=gpurun_out/ab/${name}_${cfg}_${r}.json
       # shellcheck disable=SC2086
-      timeout -k 10 300 python -u bench.py --config "$cfg" --steps "$STEPS" --warmup 2 \
+      timeout -k 10 300 python -u bench.py --full --config "$cfg" --steps "$STEPS" --warmup 2 \
         --no-cpu-baseline $args > "$out" 2> "${out%.json}.err" || exit 3
       echo "round $r $cfg $name: $(python -c "import json,sys; print(round(json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])['value'], 3))" "$out")"
     done

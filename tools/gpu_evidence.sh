@@ -15,7 +15,7 @@ tail -45 $O/pytest_gpu.log | grep -E "passed|failed|s call|s setup" | head -60
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
 [ "$CFGS" = "none" ] && exit 0
 for cfg in $CFGS; do
-  timeout -k 10 400 python -u bench.py --config "$cfg" --steps 10 --warmup 3 --no-cpu-baseline \
+  timeout -k 10 400 python -u bench.py --full --config "$cfg" --steps 10 --warmup 3 --no-cpu-baseline \
     > $O/bench_$cfg.json 2> $O/bench_$cfg.err || exit 4
   python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], round(d['value'],3), 'img/s', round(d['ms_per_step'],1), 'ms', d['roofline']['kernel'], round(d['roofline']['frac'],3))" $O/bench_$cfg.json "$cfg"
 done

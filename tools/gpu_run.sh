@@ -19,7 +19,7 @@ if [ "$SEL" != "none" ]; then
 fi
 [ "$CFGS" = "none" ] && exit 0
 for cfg in $CFGS; do
-  timeout -k 10 400 python -u bench.py --config "$cfg" --steps 10 --warmup 3 --no-cpu-baseline \
+  timeout -k 10 400 python -u bench.py --full --config "$cfg" --steps 10 --warmup 3 --no-cpu-baseline \
     > gpurun_out/bench_${cfg}_$TAG.json 2> gpurun_out/bench_${cfg}_$TAG.err || exit 4
   python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print(sys.argv[2], round(d['value'],3), 'img/s', round(d['ms_per_step'],1), 'ms', d.get('roofline',{}).get('frac'))" gpurun_out/bench_${cfg}_$TAG.json "$cfg"
 done
