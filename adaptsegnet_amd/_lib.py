@@ -144,6 +144,10 @@ _SIGS = {
     "adaptseg_add_i64": [_P, _L, _L, _P],
     "adaptseg_preprocess_workspace_size": [_I, _I, _I, _I, _I, ctypes.POINTER(_SZ)],
     "adaptseg_gta5_preprocess": [_I, _I, _I, _I, _I, _P, _F, _F, _F, _P, _P, _P, _P, _P, _SZ, _P],
+    "adaptseg_preprocess_augment_workspace_size": [_I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32),
+                                                   ctypes.POINTER(_SZ)],
+    "adaptseg_gta5_preprocess_augment": [_I, _I, _I, _I, _I, _P, _F, _F, _F, _P, _P, _P, _P,
+                                         ctypes.POINTER(ctypes.c_int32), _I, _P, _SZ, _P],
     "adaptseg_bn_bwd_affine": [_L, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _SZ, _P],
     "adaptseg_up2_relu_cat_fwd": [_I, _I, _I, _I, _I, _P, _P, _P, _P],
     "adaptseg_up2_relu_cat_bwd": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P],

@@ -704,6 +704,25 @@ def _gta5_preprocess(images, mean, out, labels, lut, labels_out):
         _p(lut) if labels is not None else None, _p(labels_out), wp, wsz, _stream()), "gta5_preprocess")
 
 
+@_op("gta5_preprocess_augment(Tensor images, float[] mean, int[] params, int ignore_label, Tensor(a!) out, "
+     "Tensor? labels, Tensor? lut, Tensor(b!)? labels_out) -> ()")
+def _gta5_preprocess_augment(images, mean, params, ignore_label, out, labels, lut, labels_out):
+    """params: the flattened host array [n][5] = (sw, sh, ox, oy, mirror) of include/adaptseg.h."""
+    n, h, w, _ = images.shape
+    oh, ow = out.shape[2], out.shape[3]
+    if len(params) != 5 * n:
+        raise RuntimeError(f"gta5_preprocess_augment: expected {5 * n} params for {n} images, got {len(params)}")
+    pa = (ctypes.c_int32 * (5 * n))(*params)
+    b = ctypes.c_size_t(0)
+    check(_lib.lib().adaptseg_preprocess_augment_workspace_size(n, h, w, oh, ow, pa, ctypes.byref(b)),
+          "preprocess_augment_workspace_size")
+    wp, wsz = _ws_args(b.value, images.device)
+    check(_lib.lib().adaptseg_gta5_preprocess_augment(
+        n, h, w, oh, ow, _p(images), float(mean[0]), float(mean[1]), float(mean[2]), _p(out), _p(labels),
+        _p(lut) if labels is not None else None, _p(labels_out), pa, int(ignore_label), wp, wsz, _stream()),
+        "gta5_preprocess_augment")
+
+
 @_op("upsample_argmax(Tensor x, Tensor(a!) out) -> ()")
 def _upsample_argmax(x, out):
     n, h, w, c = x.shape

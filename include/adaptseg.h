@@ -454,6 +454,22 @@ int adaptseg_preprocess_workspace_size(int n, int in_h, int in_w, int out_h, int
 int adaptseg_gta5_preprocess(int n, int in_h, int in_w, int out_h, int out_w, const uint8_t *rgb, float mean_b,
                              float mean_g, float mean_r, float *image, const uint8_t *label_ids, const int32_t *lut,
                              int64_t *labels, void *ws, size_t ws_bytes, adaptseg_stream_t stream);
+/* The same with a per-sample random scale, crop / pad window and horizontal mirror (the
+   augmentation the reference's --random-scale / --random-mirror flags name).  params: HOST array
+   [n][5] = (sw, sh, ox, oy, mirror).  Sample i is resized to sw x sh exactly as above, flipped
+   left-right if mirror, and out[:, y, x] = that[:, y + oy, x + ox]; where (x + ox, y + oy) lies
+   outside the sw x sh image the image gets 0.0f (a pixel equal to the mean) and the label
+   ignore_label.  A window partly or wholly outside is legal.  The scaled image is never
+   materialised: the work and the workspace follow the out_w x out_h window.  Rejected on the
+   host before any launch: sw, sh outside [1, 2^20), |ox| or |oy| >= 2^20, mirror not 0 / 1, a
+   downscale factor above 15, a NULL or short workspace (ADAPTSEG_ERR_WORKSPACE). */
+int adaptseg_preprocess_augment_workspace_size(int n, int in_h, int in_w, int out_h, int out_w,
+                                               const int32_t *params, size_t *bytes);
+int adaptseg_gta5_preprocess_augment(int n, int in_h, int in_w, int out_h, int out_w, const uint8_t *rgb,
+                                     float mean_b, float mean_g, float mean_r, float *image,
+                                     const uint8_t *label_ids, const int32_t *lut, int64_t *labels,
+                                     const int32_t *params, int ignore_label, void *ws, size_t ws_bytes,
+                                     adaptseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* MaxPool2d (model/deeplab_multi.py:135: kernel 3, stride 2, pad 1, floor mode), NHWC.  */
