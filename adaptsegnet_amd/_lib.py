@@ -60,6 +60,21 @@ class BnSumDesc(ctypes.Structure):
     ]
 
 
+FUSE_MAX_MAPS = 8
+FUSE_PROB, FUSE_LOGIT = 0, 1
+
+
+class FuseDesc(ctypes.Structure):
+    """adaptseg_fuse_desc (include/adaptseg.h)."""
+    _fields_ = [
+        ("n", ctypes.c_int), ("c", ctypes.c_int), ("oh", ctypes.c_int), ("ow", ctypes.c_int),
+        ("nmaps", ctypes.c_int), ("mode", ctypes.c_int),
+        ("h", ctypes.c_int * FUSE_MAX_MAPS), ("w", ctypes.c_int * FUSE_MAX_MAPS),
+        ("mirror", ctypes.c_int * FUSE_MAX_MAPS),
+        ("x", ctypes.c_void_p * FUSE_MAX_MAPS),
+    ]
+
+
 _P = ctypes.c_void_p
 _I = ctypes.c_int
 _L = ctypes.c_int64
@@ -112,6 +127,7 @@ _SIGS = {
     "adaptseg_bn_workspace_size": [_L, _I, ctypes.POINTER(_SZ)],
     "adaptseg_bn_fwd_train": [_L, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _P, _SZ, _P],
     "adaptseg_upsample_argmax": [_I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "adaptseg_fuse_argmax": [ctypes.POINTER(FuseDesc), _P, _P, _P],
     "adaptseg_confusion_hist": [_L, _P, _P, _P, _I, _P, _P],
     "adaptseg_bn_fwd_train_tiles": [_L, _I, _P, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _P],
     "adaptseg_conv2d_bnstats_size": [_DESC, ctypes.POINTER(ctypes.c_size_t)],

@@ -766,6 +766,229 @@ __global__ void upsample_argmax_kernel(int n, int C, int h, int w, int OH, int O
   }
 }
 
+// Multi-scale / mirrored test-time fusion: S low-resolution logit maps (each NHWC, its own
+// h x w, optionally mirrored along W) -> one class map, optionally the winning class's fused
+// probability.  One thread per output pixel; it reads the maps (cache-resident taps shared by
+// neighbouring pixels) and writes 1 (+4) bytes, against S x C x OH x OW x 4 B per intermediate
+// of the unfused composition (interp, softmax, add, argmax).  Measured: the tap loads, not the
+// bytes, set its time.
+//   PROB : f[c] = (sum_s softmax_c(v_s)[c]) * (1/S)     LOGIT: f[c] = sum_s v_s[c]
+// with v_s the bilinear align_corners=True sample of map s, coordinates and blend rounded exactly
+// as in upsample_argmax_kernel (S = 1, LOGIT is that kernel bit for bit).  No per-class array: pass 1
+// walks C per map for its max and exp-sum (2 scalars per map), pass 2 walks C once more,
+// recomputing v_s[c] for every map, and keeps a running argmax.  S is a template parameter and
+// every loop over maps is fully unrolled: the per-map taps and scalars live in registers and the
+// by-value descriptor is only read at compile-time indices (scalar kernarg loads, no scratch).
+struct FuseParams {
+  const float *x[ADAPTSEG_FUSE_MAX_MAPS];
+  int h[ADAPTSEG_FUSE_MAX_MAPS], w[ADAPTSEG_FUSE_MAX_MAPS], mirror[ADAPTSEG_FUSE_MAX_MAPS];
+  int n, C, OH, OW;
+};
+
+// ac_src and the blend of upsample_argmax_kernel with the roundings written out.  That kernel
+// leaves its contraction to the compiler, which fuses l1 = fma(scale, dst, -i0) and each row's
+// fma(1 - lx, a, lx * b) and adds the two weighted rows unfused; an instantiation for another S
+// is free to choose otherwise (packed across maps it did), so here every fma is explicit and
+// nothing else may contract: all S, both modes and both passes round alike, and S = 1 LOGIT
+// equals upsample_argmax_kernel bit for bit (tests/test_tta_gpu.py pins that).
+__device__ __forceinline__ void fuse_src(float scale, int dst, int in, int &i0, int &i1, float &l1) {
+#pragma clang fp contract(off)
+  const float src = scale * (float)dst;
+  i0 = (int)src;
+  i1 = i0 + ((i0 < in - 1) ? 1 : 0);
+  l1 = __builtin_fmaf(scale, (float)dst, -(float)i0);
+}
+
+__device__ __forceinline__ float fuse_blend(float a, float b, float d, float e, float ly, float lx) {
+#pragma clang fp contract(off)
+  const float top = __builtin_fmaf(1.f - lx, a, lx * b), bot = __builtin_fmaf(1.f - lx, d, lx * e);
+  return (1.f - ly) * top + ly * bot;
+}
+
+__device__ __forceinline__ float fuse_tap(const float *__restrict__ x, uint32_t o00, uint32_t o01, uint32_t o10,
+                                          uint32_t o11, float ly, float lx, int c) {
+  return fuse_blend(x[o00 + c], x[o01 + c], x[o10 + c], x[o11 + c], ly, lx);
+}
+
+// four consecutive classes of one tap in one 16-B load; a tap's class row is only 4-B aligned
+// (C floats per pixel), which global loads on gfx950 allow
+struct __attribute__((packed, aligned(4))) FuseQuad {
+  float v[4];
+};
+__device__ __forceinline__ FuseQuad fuse_quad(const float *__restrict__ x, uint32_t o) {
+  return *reinterpret_cast<const FuseQuad *>(x + o);
+}
+
+// The accumulation over maps stays un-contracted: exp * (1/sum) is rounded before it is added,
+// so two copies of one map fuse to exactly that map's result (p + p, then * 0.5).
+__device__ __forceinline__ float fuse_prob(float e, float inv) {
+#pragma clang fp contract(off)
+  return e * inv;
+}
+__device__ __forceinline__ float fuse_add(float f, float v) {
+#pragma clang fp contract(off)
+  return f + v;
+}
+__device__ __forceinline__ float fuse_scale(float f, float r) {
+#pragma clang fp contract(off)
+  return f * r;
+}
+
+template <int S, int MODE>
+__global__ void __launch_bounds__(256) fuse_argmax_kernel(FuseParams p, uint8_t *__restrict__ out,
+                                                          float *__restrict__ conf) {
+  const int C = p.C, OH = p.OH, OW = p.OW;
+  const int64_t total = (int64_t)p.n * OH * OW;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int X = (int)(i % OW);
+    const int64_t t = i / OW;
+    const int Y = (int)(t % OH), b = (int)(t / OH);
+    // element offsets of the four taps' class rows (host: every map has < 2^31 elements)
+    uint32_t o00[S], o01[S], o10[S], o11[S];
+    float ly[S], lx[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      const int h = p.h[s], w = p.w[s];
+      int y0, y1, x0, x1;
+      fuse_src(ac_scale(h, OH), Y, h, y0, y1, ly[s]);
+      fuse_src(ac_scale(w, OW), X, w, x0, x1, lx[s]);
+      if (p.mirror[s]) {   // flip along W, then interpolate: the same taps from mirrored columns
+        x0 = w - 1 - x0;
+        x1 = w - 1 - x1;
+      }
+      const uint32_t r0 = (uint32_t)(b * h + y0) * (uint32_t)w, r1 = (uint32_t)(b * h + y1) * (uint32_t)w;
+      o00[s] = (r0 + x0) * (uint32_t)C;
+      o01[s] = (r0 + x1) * (uint32_t)C;
+      o10[s] = (r1 + x0) * (uint32_t)C;
+      o11[s] = (r1 + x1) * (uint32_t)C;
+    }
+    float mx[S], inv[S];
+    if (MODE == ADAPTSEG_FUSE_PROB) {
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        float m = fuse_tap(p.x[s], o00[s], o01[s], o10[s], o11[s], ly[s], lx[s], 0);
+        for (int c = 1; c < C; ++c)
+          m = fmaxf(m, fuse_tap(p.x[s], o00[s], o01[s], o10[s], o11[s], ly[s], lx[s], c));
+        float sum = 0.f;
+        for (int c = 0; c < C; ++c)
+          sum += expf(fuse_tap(p.x[s], o00[s], o01[s], o10[s], o11[s], ly[s], lx[s], c) - m);
+        mx[s] = m;
+        inv[s] = 1.f / sum;
+      }
+    }
+    float best = 0.f;
+    int arg = 0;
+    for (int c = 0; c < C; ++c) {
+      float f = 0.f;
+#pragma unroll
+      for (int s = 0; s < S; ++s) {
+        float v = fuse_tap(p.x[s], o00[s], o01[s], o10[s], o11[s], ly[s], lx[s], c);
+        if (MODE == ADAPTSEG_FUSE_PROB) v = fuse_prob(expf(v - mx[s]), inv[s]);
+        f = s == 0 ? v : fuse_add(f, v);
+      }
+      if (MODE == ADAPTSEG_FUSE_PROB) f = fuse_scale(f, 1.f / (float)S);
+      if (c == 0 || (!isnan(best) && (f > best || isnan(f)))) {
+        best = f;
+        arg = c;
+      }
+    }
+    out[i] = (uint8_t)arg;
+    if (MODE == ADAPTSEG_FUSE_PROB && conf) conf[i] = best;
+  }
+}
+
+// PROB mode for C <= kFuseRegC classes (Cityscapes 19, VOC 21): the same arithmetic in the same
+// order, bit for bit, with each map's scores and the fused probabilities in registers, so every
+// tap is loaded once, four classes per 16-B load, and every exponential taken once (the kernel
+// above reads the taps three times, a dword at a time; the tap loads, not the output bytes, set
+// its time).  The class loops are unrolled to
+// kFuseRegC with a uniform `c < C` guard, so both arrays are indexed at compile time only.  The
+// map loop stays a run-time loop (one body, one kernel for every S): map s's descriptor entries
+// come out of a fully unrolled compare chain, so the by-value struct is still read at constant
+// offsets.
+constexpr int kFuseRegC = 32;
+__global__ void __launch_bounds__(256) fuse_prob_regs_kernel(FuseParams p, int S, uint8_t *__restrict__ out,
+                                                             float *__restrict__ conf) {
+  const int C = p.C, OH = p.OH, OW = p.OW;
+  const int64_t total = (int64_t)p.n * OH * OW;
+  const float rs = 1.f / (float)S;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
+       i += (int64_t)gridDim.x * blockDim.x) {
+    const int X = (int)(i % OW);
+    const int64_t t = i / OW;
+    const int Y = (int)(t % OH), b = (int)(t / OH);
+    float f[kFuseRegC];
+#pragma unroll
+    for (int c = 0; c < kFuseRegC; ++c) f[c] = 0.f;   // 0 + p is p: the first map adds exactly
+#pragma unroll 1
+    for (int s = 0; s < S; ++s) {
+      const float *x = p.x[0];
+      int h = p.h[0], w = p.w[0], mirror = p.mirror[0];
+#pragma unroll
+      for (int k = 1; k < ADAPTSEG_FUSE_MAX_MAPS; ++k) {
+        x = s == k ? p.x[k] : x;
+        h = s == k ? p.h[k] : h;
+        w = s == k ? p.w[k] : w;
+        mirror = s == k ? p.mirror[k] : mirror;
+      }
+      int y0, y1, x0, x1;
+      float ly, lx;
+      fuse_src(ac_scale(h, OH), Y, h, y0, y1, ly);
+      fuse_src(ac_scale(w, OW), X, w, x0, x1, lx);
+      if (mirror) {
+        x0 = w - 1 - x0;
+        x1 = w - 1 - x1;
+      }
+      const uint32_t r0 = (uint32_t)(b * h + y0) * (uint32_t)w, r1 = (uint32_t)(b * h + y1) * (uint32_t)w;
+      const uint32_t o00 = (r0 + x0) * (uint32_t)C, o01 = (r0 + x1) * (uint32_t)C;
+      const uint32_t o10 = (r1 + x0) * (uint32_t)C, o11 = (r1 + x1) * (uint32_t)C;
+      float v[kFuseRegC];
+      float m = 0.f;
+#pragma unroll
+      for (int c = 0; c < kFuseRegC; c += 4) {
+        if (c + 3 < C) {
+          const FuseQuad a = fuse_quad(x, o00 + c), q = fuse_quad(x, o01 + c);
+          const FuseQuad d = fuse_quad(x, o10 + c), e = fuse_quad(x, o11 + c);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[c + j] = fuse_blend(a.v[j], q.v[j], d.v[j], e.v[j], ly, lx);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (c + j < C) v[c + j] = fuse_tap(x, o00, o01, o10, o11, ly, lx, c + j);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < kFuseRegC; ++c)
+        if (c < C) m = c == 0 ? v[c] : fmaxf(m, v[c]);
+      float sum = 0.f;
+#pragma unroll
+      for (int c = 0; c < kFuseRegC; ++c)
+        if (c < C) {
+          v[c] = expf(v[c] - m);
+          sum += v[c];
+        }
+      const float inv = 1.f / sum;
+#pragma unroll
+      for (int c = 0; c < kFuseRegC; ++c)
+        if (c < C) f[c] = fuse_add(f[c], fuse_prob(v[c], inv));
+    }
+    float best = 0.f;
+    int arg = 0;
+#pragma unroll
+    for (int c = 0; c < kFuseRegC; ++c)
+      if (c < C) {
+        const float fc = fuse_scale(f[c], rs);
+        if (c == 0 || (!isnan(best) && (fc > best || isnan(fc)))) {
+          best = fc;
+          arg = c;
+        }
+      }
+    out[i] = (uint8_t)arg;
+    if (conf) conf[i] = best;
+  }
+}
+
 // hist[gt][pred] += 1 over pixels whose (LUT-mapped) label is in [0, n): compute_iou's
 // label_mapping + fast_hist.  Per-block LDS bins, then one 64-bit atomic per non-zero bin
 // (integer adds: the result is exact and order-independent).
@@ -788,6 +1011,19 @@ __global__ void __launch_bounds__(256) confusion_hist_kernel(int64_t npix, const
     if (bins[j]) atomicAdd(&hist[j], (unsigned long long)bins[j]);
 }
 
+template <int MODE>
+static void launch_fuse(int nmaps, int blocks, hipStream_t st, const FuseParams &p, uint8_t *out, float *conf) {
+  switch (nmaps) {
+#define AS_FUSE_CASE(S)                                                          \
+  case S:                                                                        \
+    fuse_argmax_kernel<S, MODE><<<blocks, 256, 0, st>>>(p, out, conf);           \
+    break;
+    AS_FUSE_CASE(1) AS_FUSE_CASE(2) AS_FUSE_CASE(3) AS_FUSE_CASE(4)
+    AS_FUSE_CASE(5) AS_FUSE_CASE(6) AS_FUSE_CASE(7) AS_FUSE_CASE(8)
+#undef AS_FUSE_CASE
+  }
+}
+
 }  // namespace adaptseg
 
 using namespace adaptseg;
@@ -801,6 +1037,43 @@ int adaptseg_upsample_argmax(int n, int c, int h, int w, int oh, int ow, const f
   const int64_t total = (int64_t)n * oh * ow;
   upsample_argmax_kernel<<<grid1d(total), 256, 0, as_stream(stream)>>>(n, c, h, w, oh, ow, x, out);
   AS_CHECK_LAUNCH("upsample_argmax");
+  return ADAPTSEG_OK;
+}
+
+int adaptseg_fuse_argmax(const adaptseg_fuse_desc *d, uint8_t *out, float *conf, adaptseg_stream_t stream) {
+  AS_CHECK_ARG(d, "fuse_argmax: bad args (null descriptor)");
+  AS_CHECK_ARG(d->nmaps >= 1 && d->nmaps <= ADAPTSEG_FUSE_MAX_MAPS, "fuse_argmax: bad nmaps %d (1..%d)", d->nmaps,
+               ADAPTSEG_FUSE_MAX_MAPS);
+  AS_CHECK_ARG(d->n > 0 && d->c > 0 && d->oh > 0 && d->ow > 0, "fuse_argmax: bad dims n %d c %d out %dx%d", d->n,
+               d->c, d->oh, d->ow);
+  AS_CHECK_ARG(d->c <= 256, "fuse_argmax: bad c %d (at most 256 classes)", d->c);
+  AS_CHECK_ARG(d->mode == ADAPTSEG_FUSE_PROB || d->mode == ADAPTSEG_FUSE_LOGIT, "fuse_argmax: bad mode %d", d->mode);
+  AS_CHECK_ARG(out, "fuse_argmax: bad args (null out)");
+  AS_CHECK_ARG(!(conf && d->mode == ADAPTSEG_FUSE_LOGIT),
+               "fuse_argmax: bad args (conf is the fused probability: PROB mode only)");
+  FuseParams p = {};
+  for (int s = 0; s < d->nmaps; ++s) {
+    AS_CHECK_ARG(d->h[s] > 0 && d->w[s] > 0, "fuse_argmax: bad size %dx%d of map %d", d->h[s], d->w[s], s);
+    AS_CHECK_ARG(d->x[s], "fuse_argmax: bad args (null map %d)", s);
+    AS_CHECK_ARG((int64_t)d->n * d->h[s] * d->w[s] * d->c < (1ll << 31),
+                 "fuse_argmax: bad size of map %d (2^31 elements or more)", s);
+    p.x[s] = d->x[s];
+    p.h[s] = d->h[s];
+    p.w[s] = d->w[s];
+    p.mirror[s] = d->mirror[s] != 0;
+  }
+  p.n = d->n;
+  p.C = d->c;
+  p.OH = d->oh;
+  p.OW = d->ow;
+  const int blocks = grid1d((int64_t)d->n * d->oh * d->ow, 256, 2048);
+  if (d->mode == ADAPTSEG_FUSE_PROB && d->c <= kFuseRegC)
+    fuse_prob_regs_kernel<<<blocks, 256, 0, as_stream(stream)>>>(p, d->nmaps, out, conf);
+  else if (d->mode == ADAPTSEG_FUSE_PROB)
+    launch_fuse<ADAPTSEG_FUSE_PROB>(d->nmaps, blocks, as_stream(stream), p, out, conf);
+  else
+    launch_fuse<ADAPTSEG_FUSE_LOGIT>(d->nmaps, blocks, as_stream(stream), p, out, conf);
+  AS_CHECK_LAUNCH("fuse_argmax");
   return ADAPTSEG_OK;
 }
 

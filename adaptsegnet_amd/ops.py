@@ -730,6 +730,27 @@ def _upsample_argmax(x, out):
           "upsample_argmax")
 
 
+@_op("fuse_argmax(Tensor[] maps, int[] mirror, int mode, Tensor(a!) out, Tensor(b!)? conf) -> ()")
+def _fuse_argmax(maps, mirror, mode, out, conf):
+    """maps: NHWC fp32 buffers [n, h_s, w_s, c]; mirror: one flag per map; mode: _lib.FUSE_PROB / FUSE_LOGIT."""
+    if not 1 <= len(maps) <= _lib.FUSE_MAX_MAPS or len(mirror) != len(maps):
+        raise RuntimeError(f"fuse_argmax: {len(maps)} maps (1..{_lib.FUSE_MAX_MAPS}) with {len(mirror)} mirror flags")
+    n, _, _, c = maps[0].shape
+    d = _lib.FuseDesc()
+    d.n, d.c, d.oh, d.ow, d.nmaps, d.mode = n, c, out.shape[1], out.shape[2], len(maps), int(mode)
+    for s, x in enumerate(maps):
+        if x.dim() != 4 or x.shape[0] != n or x.shape[3] != c or not x.is_contiguous():
+            raise RuntimeError(f"fuse_argmax: map {s} is {tuple(x.shape)}, expected a contiguous [{n}, h, w, {c}]")
+        d.h[s], d.w[s], d.mirror[s] = x.shape[1], x.shape[2], int(bool(mirror[s]))
+        d.x[s] = _pf(x, x.numel(), f"fuse_argmax map {s}").value
+    if out.dtype != torch.uint8 or out.shape[0] != n or not out.is_contiguous():
+        raise RuntimeError(f"fuse_argmax: out is {out.dtype} {tuple(out.shape)}, expected contiguous uint8 [{n}, H, W]")
+    if conf is not None and (conf.shape != out.shape or not conf.is_contiguous()):
+        raise RuntimeError(f"fuse_argmax: conf is {tuple(conf.shape)}, expected contiguous {tuple(out.shape)}")
+    check(_lib.lib().adaptseg_fuse_argmax(ctypes.byref(d), _p(out), _pf(conf, out.numel(), "fuse_argmax conf"),
+                                          _stream()), "fuse_argmax")
+
+
 @_op("confusion_hist(Tensor gt_ids, Tensor lut, Tensor pred, int num_classes, Tensor(a!) hist) -> ()")
 def _confusion_hist(gt_ids, lut, pred, num_classes, hist):
     check(_lib.lib().adaptseg_confusion_hist(gt_ids.numel(), _p(gt_ids), _p(lut), _p(pred), int(num_classes),

@@ -436,6 +436,28 @@ int adaptseg_bn_bwd_affine(int64_t rows, int c, const float *dy, const float *y,
 /* out[n][oh][ow] = argmax_c bilinear_align_corners(x)[n][oh][ow][c]; x NHWC [n][h][w][c]. */
 int adaptseg_upsample_argmax(int n, int c, int h, int w, int oh, int ow, const float *x,
                              uint8_t *out, adaptseg_stream_t stream);
+/* Multi-scale / mirrored test-time fusion (the DeepLab-v2 evaluation protocol) in one launch:
+   nmaps logit maps x[s], contiguous NHWC fp32 [n][h[s]][w[s]][c], -> out[n][oh][ow] (uint8) and,
+   optionally, conf[n][oh][ow] (fp32).  Per output pixel, v_s[c] is the bilinear
+   align_corners=True sample of map s (coordinates and blend as adaptseg_upsample_argmax); with
+   mirror[s] != 0 the two column taps are read from w-1-x0 and w-1-x1, which is bit for bit
+   "flip the map along W, then interpolate".
+     ADAPTSEG_FUSE_PROB : f[c] = (sum_s softmax_c(v_s)[c]) * (1/nmaps)  (fp32, max-subtracted,
+                          summed in map order)
+     ADAPTSEG_FUSE_LOGIT: f[c] = sum_s v_s[c]   (nmaps == 1: adaptseg_upsample_argmax, bit for bit)
+   out = the first maximal class of f (a NaN wins over numbers); conf (PROB only, may be NULL) =
+   f[out], the fused probability of the winning class.  Rejected on the host before any launch
+   (ADAPTSEG_ERR_ARG): nmaps outside 1..ADAPTSEG_FUSE_MAX_MAPS, a non-positive dimension,
+   c > 256, a map of 2^31 elements or more, a NULL map or out, an unknown mode, conf in LOGIT mode. */
+#define ADAPTSEG_FUSE_MAX_MAPS 8
+#define ADAPTSEG_FUSE_PROB 0
+#define ADAPTSEG_FUSE_LOGIT 1
+typedef struct adaptseg_fuse_desc {
+  int n, c, oh, ow, nmaps, mode;
+  int h[ADAPTSEG_FUSE_MAX_MAPS], w[ADAPTSEG_FUSE_MAX_MAPS], mirror[ADAPTSEG_FUSE_MAX_MAPS];
+  const float *x[ADAPTSEG_FUSE_MAX_MAPS];
+} adaptseg_fuse_desc;
+int adaptseg_fuse_argmax(const adaptseg_fuse_desc *d, uint8_t *out, float *conf, adaptseg_stream_t stream);
 /* hist[a][b] += #pixels with a = lut[gt] (or gt if lut == NULL) in [0, ncls), b = pred;
    hist is int64 [ncls][ncls] (accumulated, never cleared). */
 int adaptseg_confusion_hist(int64_t npix, const uint8_t *gt, const int32_t *lut,
