@@ -129,6 +129,9 @@ _SIGS = {
     "adaptseg_upsample_argmax": [_I, _I, _I, _I, _I, _I, _P, _P, _P],
     "adaptseg_fuse_argmax": [ctypes.POINTER(FuseDesc), _P, _P, _P],
     "adaptseg_confusion_hist": [_L, _P, _P, _P, _I, _P, _P],
+    "adaptseg_conf_hist": [_L, _P, _P, _I, _I, _P, _P],
+    "adaptseg_pseudo_thresholds": [_P, _I, _I, ctypes.c_double, _F, _P, _P],
+    "adaptseg_pseudo_label": [_L, _P, _P, _P, _I, _I, _P, _P, _P],
     "adaptseg_bn_fwd_train_tiles": [_L, _I, _P, _I, _P, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _I, _P],
     "adaptseg_conv2d_bnstats_size": [_DESC, ctypes.POINTER(ctypes.c_size_t)],
     "adaptseg_conv2d_bnstats_tiles": [_DESC, ctypes.POINTER(_I)],

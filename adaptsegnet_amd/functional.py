@@ -47,13 +47,16 @@ def softmax2d(x: torch.Tensor) -> torch.Tensor:
 
 class _CrossEntropy2d(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, logits, labels, ignore, weight, total):
+    def forward(ctx, logits, labels, ignore, weight, reduction):
         x = K.nhwc_view(logits)
         out = K.ce_fwd(x, labels, ignore, weight)   # [mean, denominator]
         ctx.save_for_backward(x, labels, out, weight)
-        ctx.ignore, ctx.total = ignore, total
-        if total:   # reduction='sum': mean * denominator; an empty selection sums to 0
+        ctx.ignore, ctx.total = ignore, reduction == "sum"
+        if ctx.total:   # reduction='sum': mean * denominator; an empty selection sums to 0
             return torch.where(out[1] > 0, out[0] * out[1], torch.zeros_like(out[0]))
+        if reduction == "mean_or_zero":   # the mean, and 0 (not 0/0) over an empty selection; its
+            # gradient needs nothing more: the backward kernels write 0 for every ignored pixel
+            return torch.where(out[1] > 0, out[0], torch.zeros_like(out[0]))
         return out[0]
 
     @staticmethod
@@ -72,11 +75,13 @@ def cross_entropy2d(logits: torch.Tensor, labels: torch.Tensor, ignore_index: in
     """Softmax cross entropy over pixels whose label is >= 0 and != ignore_index.
 
     logits: [N, C, H, W] fp32; labels: [N, H, W] int64.  reduction 'mean' (weighted by
-    ``weight[label]`` when given) or 'sum'.  Returns a 0-dim device tensor; an all-ignored
-    batch gives NaN for the mean (like the reference) and 0 for the sum (F.cross_entropy).
+    ``weight[label]`` when given), 'sum' or 'mean_or_zero'.  Returns a 0-dim device tensor; an
+    all-ignored batch gives NaN for the mean (like the reference) and 0 for the sum
+    (F.cross_entropy); 'mean_or_zero' is the mean, but 0 with a zero gradient for an all-ignored
+    batch (the self-training term: a batch of pseudo-labels may keep no pixel).
     """
-    if reduction not in ("mean", "sum"):
-        raise ValueError(f"cross_entropy2d: reduction {reduction!r} (expected 'mean' or 'sum')")
+    if reduction not in ("mean", "sum", "mean_or_zero"):
+        raise ValueError(f"cross_entropy2d: reduction {reduction!r} (expected 'mean', 'sum' or 'mean_or_zero')")
     _check(logits, "cross_entropy2d")
     if labels.dtype != torch.int64:
         raise RuntimeError(f"cross_entropy2d: labels must be int64 (got {labels.dtype})")
@@ -86,7 +91,7 @@ def cross_entropy2d(logits: torch.Tensor, labels: torch.Tensor, ignore_index: in
     labels = labels.contiguous()
     if weight is not None:
         weight = weight.to(device=logits.device, dtype=torch.float32).contiguous()
-    return _CrossEntropy2d.apply(logits, labels, int(ignore_index), weight, reduction == "sum")
+    return _CrossEntropy2d.apply(logits, labels, int(ignore_index), weight, reduction)
 
 
 class _AdvLoss(torch.autograd.Function):

@@ -23,6 +23,11 @@ passed as the initial gradient of ``backward`` instead of multiplying the loss t
 constant label tensors (:621, ...) are folded into the loss kernels, and the per-loss
 ``.item()`` host syncs are deferred to ``StepLosses.values()``.
 
+Beyond the reference: ``StepConfig.lambda_st > 0`` adds a self-training term to the target branch,
+the cross entropy of the target prediction(s) against pseudo-labels given as a fourth batch
+element (adaptsegnet_amd/pseudo.py; the CBST / BDL stage after adaptation).  At 0, the default,
+the step is the reference's.
+
 Data parallel (one process per GPU): every rank runs the step on its own shard, and SUM
 all-reduces of the gradient arenas replace DataParallel's gradient gather
 (train_gta2cityscapes_multi.py:224-225); the 1/world average is folded into the optimiser.
@@ -65,6 +70,13 @@ class StepConfig:
     lambda_adv_target1: float = 0.0002
     lambda_adv_target2: float = 0.001
     ignore_label: int = 255
+    # self-training (the CBST / BDL stage after adaptation): with lambda_st > 0 every batch is
+    # (images, labels, images_target, labels_target) and the target branch adds
+    # lambda_st * CE(pred_target2, labels_target) (multi-level: + lambda_seg * lambda_st * CE on
+    # pred_target1), the mean over the pixels that are not ``ignore_label``, 0 when none is left.
+    # labels_target: int64 [N, H, W] at the size the target prediction is upsampled to
+    # (``_target_size()``), e.g. adaptsegnet_amd.pseudo.pseudo_labels.  0: the step as it was
+    lambda_st: float = 0.0
     # run the target-domain generator forward (+ its D forward) on a second HIP stream while
     # the source-domain backward executes (independent: same weights, read-only, separate
     # gradient kernels); the target backward then waits for the source backward.  Results are
@@ -125,6 +137,11 @@ class AdaptSegTrainer:
             raise ValueError("multi-level needs model_D1")
         if cfg.level == "multi-level" and getattr(model, "single_output", False):
             raise ValueError("multi-level needs a two-head generator (DeeplabMulti)")
+        if cfg.lambda_st < 0:
+            raise ValueError(f"lambda_st {cfg.lambda_st!r} (expected >= 0)")
+        if cfg.lambda_st > 0 and cfg.level == "source-only":
+            raise ValueError("lambda_st > 0: the self-training term belongs to the target branch of the "
+                             "single-level / multi-level steps; the source-only step has none")
         if cfg.level != "source-only" and model_D2 is None:
             raise ValueError(f"{cfg.level} needs model_D2")
         if warper is not None and (cfg.level == "multi-level" or getattr(model, "single_output", False)):
@@ -341,13 +358,19 @@ class AdaptSegTrainer:
         return L
 
     def _step_body(self, i_iter, batches):
-        """batches: iterable of ``iter_size`` tuples (images, labels, images_target).
+        """batches: iterable of ``iter_size`` tuples (images, labels, images_target), or with
+        ``cfg.lambda_st > 0`` (images, labels, images_target, labels_target).
 
         Multi-GPU: the generator's gradients are final after its adversarial backward of the
         last sub-iteration, so their all-reduce (the 178 MB arena) is launched right there and
         overlaps the discriminator forward/backward passes; the discriminators' (11 MB each)
         follow their last backward.  The optimisers wait for both."""
         c = self.cfg
+        batches = list(batches)
+        tsize = self._target_size()
+        if c.lambda_st > 0:   # a malformed self-training batch raises before anything is launched
+            for batch in batches:
+                self._st_labels(batch, tsize)
         L = StepLosses()
         self.opt.zero_grad()
         for o in (self.opt_D1, self.opt_D2):
@@ -355,19 +378,18 @@ class AdaptSegTrainer:
                 o.zero_grad()
         self.adjust_learning_rate(i_iter)
         inv = 1.0 / c.iter_size
-        tsize = self._target_size()
-        batches = list(batches)
         self._pending = []
         for idx, batch in enumerate(batches):
             g_done = _GSync(self) if idx == len(batches) - 1 else None
             if c.level == "source-only":
                 self._sub_source_only(batch[0], batch[1], inv, L, g_done)
                 continue
-            images, labels, images_t = batch
+            images, labels, images_t = batch[:3]
+            labels_t = batch[3] if c.lambda_st > 0 else None
             if c.level == "single-level":
-                self._sub_single(images, labels, images_t, inv, tsize, L, g_done)
+                self._sub_single(images, labels, images_t, inv, tsize, L, g_done, labels_t)
             else:
-                self._sub_multi(images, labels, images_t, inv, tsize, L, g_done)
+                self._sub_multi(images, labels, images_t, inv, tsize, L, g_done, labels_t)
         if not batches:
             self._start_sync((self.model,))
         if batches and c.level != "source-only":
@@ -380,6 +402,28 @@ class AdaptSegTrainer:
             if o is not None:
                 o.step(grad_scale=gs)
         return L
+
+    @staticmethod
+    def _st_labels(batch, tsize):
+        """The fourth element of a self-training batch, checked against the target prediction's size."""
+        if len(batch) != 4:
+            raise ValueError(f"lambda_st > 0: every batch is (images, labels, images_target, labels_target); "
+                             f"got {len(batch)} elements")
+        images_t, labels_t = batch[2], batch[3]
+        want = (images_t.shape[0], int(tsize[1]), int(tsize[0]))
+        if labels_t.dtype != torch.int64 or tuple(labels_t.shape) != want:
+            raise ValueError(f"labels_target is {labels_t.dtype} {tuple(labels_t.shape)}: expected int64 {want}, "
+                             f"[N, H, W] at the size the target prediction is upsampled to (W, H) = {tuple(tsize)}")
+        return labels_t
+
+    def _st_loss(self, pred_target, labels_t, ov):
+        """CE of a target prediction against the pseudo-labels, on the stream the target branch runs
+        on.  ``labels_t`` was made on the caller's stream, which the step's streams are ordered
+        after (step(): hp.wait_stream; _target_ctx: the side stream waits for the main one); it is
+        marked used on the side stream like the other tensors that cross streams."""
+        if ov is not None:
+            labels_t.record_stream(ov[1])
+        return F.cross_entropy2d(pred_target, labels_t, self.cfg.ignore_label, reduction="mean_or_zero")
 
     def _pred_single(self, images, size, flow=None):
         """The single-level prediction at ``size`` = (W, H): DeeplabMulti's second head (warped
@@ -406,7 +450,7 @@ class AdaptSegTrainer:
         if g_done is not None:
             g_done.end()
 
-    def _sub_single(self, images, labels, images_t, inv, tsize, L, g_done=None):
+    def _sub_single(self, images, labels, images_t, inv, tsize, L, g_done=None, labels_t=None):
         """train_gta2cityscapes_multi.py:385-461."""
         c, D2 = self.cfg, self.D2
         self._set_requires_grad(D2, False)
@@ -419,15 +463,16 @@ class AdaptSegTrainer:
         def target_forward():
             with self._target_ctx(ov):
                 pt2 = self._pred_single(images_t, tsize, None if flow is None else flow.detach())
-                return pt2, F.adv_loss(self._d_out(D2, F.softmax2d(pt2), keep2), 0.0, self.kind)
+                adv2 = F.adv_loss(self._d_out(D2, F.softmax2d(pt2), keep2), 0.0, self.kind)
+                return pt2, adv2, ([] if labels_t is None else [self._st_loss(pt2, labels_t, ov)])
 
         first = ov is not None and c.target_first
         if first:
-            pred_target2, loss_adv_target2 = target_forward()
+            pred_target2, loss_adv_target2, loss_st = target_forward()
         self._backward([loss_seg2], [inv])
         L.add("loss_seg2", loss_seg2, inv)
         if not first:
-            pred_target2, loss_adv_target2 = target_forward()
+            pred_target2, loss_adv_target2, loss_st = target_forward()
 
         with self._target_ctx(ov):
             dev_ = loss_adv_target2.device
@@ -435,11 +480,14 @@ class AdaptSegTrainer:
             self._join_source(ov)
             if g_done is not None:
                 g_done.begin()
-            self._backward([loss_adv_target2], [c.lambda_adv_target2 * inv])
+            self._backward([loss_adv_target2] + loss_st,
+                           [c.lambda_adv_target2 * inv] + [c.lambda_st * inv] * len(loss_st))
             L.add("loss_adv_target2", loss_adv_target2, inv)
+            for t in loss_st:
+                L.add("loss_st2", t, inv)
             if g_done is not None:
                 g_done.end()
-        self._overlap_end(ov, pred_target2, loss_adv_target2, *self._kept(keep2))
+        self._overlap_end(ov, pred_target2, loss_adv_target2, *loss_st, *self._kept(keep2))
 
         self._set_requires_grad(D2, True)
         pred2 = pred2.detach()
@@ -452,7 +500,7 @@ class AdaptSegTrainer:
             self._backward([loss_d2], [inv / 2])
             L.add("loss_D2", loss_d2, inv / 2)
 
-    def _sub_multi(self, images, labels, images_t, inv, tsize, L, g_done=None):
+    def _sub_multi(self, images, labels, images_t, inv, tsize, L, g_done=None, labels_t=None):
         """train_gta2cityscapes_multi.py:578-679."""
         c, D1, D2 = self.cfg, self.D1, self.D2
         self._set_requires_grad(D1, False)
@@ -466,17 +514,19 @@ class AdaptSegTrainer:
         def target_forward():
             with self._target_ctx(ov):
                 pt1, pt2 = self.model(images_t, tsize)
-                return (pt1, pt2, F.adv_loss(self._d_out(D1, F.softmax2d(pt1), keep1), 0.0, self.kind),
-                        F.adv_loss(self._d_out(D2, F.softmax2d(pt2), keep2), 0.0, self.kind))
+                adv1 = F.adv_loss(self._d_out(D1, F.softmax2d(pt1), keep1), 0.0, self.kind)
+                adv2 = F.adv_loss(self._d_out(D2, F.softmax2d(pt2), keep2), 0.0, self.kind)
+                st = [] if labels_t is None else [self._st_loss(pt1, labels_t, ov), self._st_loss(pt2, labels_t, ov)]
+                return pt1, pt2, adv1, adv2, st
 
         first = ov is not None and c.target_first
         if first:
-            pred_target1, pred_target2, loss_adv1, loss_adv2 = target_forward()
+            pred_target1, pred_target2, loss_adv1, loss_adv2, loss_st = target_forward()
         self._backward([loss_seg2, loss_seg1], [inv, c.lambda_seg * inv])
         L.add("loss_seg1", loss_seg1, inv)
         L.add("loss_seg2", loss_seg2, inv)
         if not first:
-            pred_target1, pred_target2, loss_adv1, loss_adv2 = target_forward()
+            pred_target1, pred_target2, loss_adv1, loss_adv2, loss_st = target_forward()
 
         with self._target_ctx(ov):
             dev_ = loss_adv2.device
@@ -484,13 +534,17 @@ class AdaptSegTrainer:
             self._join_source(ov)
             if g_done is not None:
                 g_done.begin()
-            self._backward([loss_adv1, loss_adv2],
-                           [c.lambda_adv_target1 * inv, c.lambda_adv_target2 * inv])
+            st_scales = [c.lambda_seg * c.lambda_st * inv, c.lambda_st * inv][:len(loss_st)]
+            self._backward([loss_adv1, loss_adv2] + loss_st,
+                           [c.lambda_adv_target1 * inv, c.lambda_adv_target2 * inv] + st_scales)
             L.add("loss_adv_target1", loss_adv1, inv)
             L.add("loss_adv_target2", loss_adv2, inv)
+            for name, t in zip(("loss_st1", "loss_st2"), loss_st):
+                L.add(name, t, inv)
             if g_done is not None:
                 g_done.end()
-        self._overlap_end(ov, pred_target1, pred_target2, loss_adv1, loss_adv2, *self._kept(keep1, keep2))
+        self._overlap_end(ov, pred_target1, pred_target2, loss_adv1, loss_adv2, *loss_st,
+                          *self._kept(keep1, keep2))
 
         self._set_requires_grad(D1, True)
         self._set_requires_grad(D2, True)

@@ -464,6 +464,32 @@ int adaptseg_confusion_hist(int64_t npix, const uint8_t *gt, const int32_t *lut,
                             const uint8_t *pred, int ncls, int64_t *hist, adaptseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Class-balanced pseudo-labels for self-training (the CBST / BDL recipe) on the class map  */
+/* and confidence map of adaptseg_fuse_argmax.  Integer atomics only: every count is exact  */
+/* and order-independent.  A pixel is VALID when pred < ncls and conf >= 0 (a NaN or a      */
+/* negative confidence is not); invalid pixels are counted nowhere and labelled ignore.     */
+/* Rejected on the host before any launch (ADAPTSEG_ERR_ARG): a NULL pointer with npix > 0, */
+/* nbins not a power of two in 2..4096, ncls outside 1..256, portion or cap outside (0, 1], */
+/* ignore_label outside 0..255.  npix == 0 returns ADAPTSEG_OK without a launch.            */
+/* ------------------------------------------------------------------------------------ */
+/* hist[pred][bin] += 1 per valid pixel; bin = nbins-1 if conf >= 1, else (int)(conf * (float)nbins)
+   (an exact fp32 product: nbins is a power of two).  hist is int64 [ncls][nbins], accumulated,
+   never cleared. */
+int adaptseg_conf_hist(int64_t npix, const uint8_t *pred, const float *conf, int ncls, int nbins,
+                       int64_t *hist, adaptseg_stream_t stream);
+/* Per class c, T = sum_b hist[c][b]: thr[c] = cap if T == 0; else K = (int64)ceil(portion * (double)T),
+   b* = the largest bin whose suffix sum (over b >= b*) is >= K, thr[c] = min((float)b* / (float)nbins, cap).
+   One launch, no host sync. */
+int adaptseg_pseudo_thresholds(const int64_t *hist, int ncls, int nbins, double portion, float cap,
+                               float *thr, adaptseg_stream_t stream);
+/* labels[i] = pred[i] if the pixel is valid and conf[i] >= thr[pred[i]], else ignore_label (int64:
+   the labels of adaptseg_softmax_ce_fwd); kept[c] += the pixels kept for class c (int64 [ncls],
+   accumulated; may be NULL). */
+int adaptseg_pseudo_label(int64_t npix, const uint8_t *pred, const float *conf, const float *thr,
+                          int ncls, int ignore_label, int64_t *labels, int64_t *kept,
+                          adaptseg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Input pipeline: GTA5DataSet.__getitem__ after file decode (dataset/gta5_dataset.py:47-71) */
 /* and the target loader's image path (train_gta2cityscapes_multi.py:333-336, 520-523).    */
 /* Bit-exact with Pillow's Image.resize(crop, BICUBIC) / (crop, NEAREST) 8-bit resampler.   */
