@@ -2,8 +2,9 @@
 // Reference: nn.BatchNorm2d(affine, frozen) + ReLU + residual add in
 // model/deeplab_multi.py:65-101 (Bottleneck), :130-134 (stem), :160-162 (downsample).
 //
-// Forward = stats pass (per-block shifted sums -> fp64 combine, one deterministic finalize
-// that also updates running_mean / running_var with the unbiased variance, as torch does)
+// Forward = stats pass (per-thread fp32 sums of d and d^2, d = x - x[0][c] -> fp64 combine, one
+// deterministic finalize, which re-sums a channel whose pivot x[0][c] turns out to lie far from
+// its mean, and also updates running_mean / running_var with the unbiased variance, as torch does)
 // + one fused apply pass y = relu(xhat*w + b + res).  Backward = one reduction pass
 // (sum g, sum g*(x-mean), with g = dy * [y > 0] when the forward had a ReLU) + one apply
 // pass that also emits the residual gradient.  All passes are float4-vectorised and
@@ -311,6 +312,16 @@ __device__ __forceinline__ void wave_sum2(const float *p1, const float *p2, int 
   }
 }
 
+// The shifted sums are well conditioned only while the pivot x[0][c] (the corner pixel of image 0)
+// is typical of its channel: with the pivot k standard deviations from the mean, var = s2/n - dm^2
+// loses about k^2 * 2^-22 of its value to the fp32 rounding of d^2 (measured: x ~ N(5, 1), 4099
+// rows, row 0 at 15 / at 105: invstd off by 1.1e-5 / 3.0e-4, against 2e-7 with that value in any
+// other row).  Past kPivotFar standard deviations the finalize re-sums the channel in fp64 about
+// the mean it has just found (which is accurate: the conditioning only hurts the variance).  A
+// wave reads one channel, 4 B out of every row, so this costs far more per channel than the
+// reduction pass; typical data never takes it (6 sigma), and takes the parent scheme's exact sums.
+constexpr double kPivotFar = 6.0;
+
 // Finalise forward statistics: mean, invstd, running-stat update.  Block = 256 = 4 channels.
 template <typename TX>
 __global__ void bn_stats_final_kernel(int64_t rows, int C, int splits, const TX *__restrict__ x,
@@ -321,12 +332,31 @@ __global__ void bn_stats_final_kernel(int64_t rows, int C, int splits, const TX 
   if (c >= C) return;
   double s1, s2;
   wave_sum2(partial + (size_t)c * splits, partial + ((size_t)C + c) * splits, splits, s1, s2);
-  if ((threadIdx.x & 63) != 0) return;
+  const int lane = threadIdx.x & 63;
   double n = (double)rows;
+  double piv = (double)lda1(x + c);
   double dm = s1 / n;
   double var = s2 / n - dm * dm;
   if (var < 0) var = 0;
-  double mean = (double)lda1(x + c) + dm;
+  if (dm * dm > kPivotFar * kPivotFar * var) {   // (the same on all lanes: s1, s2 are wave sums)
+    piv = (double)(float)(piv + dm);
+    double t1 = 0.0, t2 = 0.0;
+    for (int64_t r = lane; r < rows; r += 64) {
+      const double d = (double)lda1(x + r * C + c) - piv;
+      t1 += d;
+      t2 += d * d;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      t1 += __shfl_xor(t1, o);
+      t2 += __shfl_xor(t2, o);
+    }
+    dm = t1 / n;
+    var = t2 / n - dm * dm;
+    if (var < 0) var = 0;
+  }
+  if (lane != 0) return;
+  double mean = piv + dm;
   mean_out[c] = (float)mean;
   invstd_out[c] = (float)(1.0 / sqrt(var + (double)eps));
   if (running_mean) running_mean[c] = (float)((1.0 - momentum) * running_mean[c] + momentum * mean);

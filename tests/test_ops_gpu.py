@@ -1,4 +1,6 @@
-"""GPU parity of every HIP kernel against the fp64 CPU oracle (torch CPU ops).
+"""GPU parity of the HIP kernels against the fp64 CPU oracle (torch CPU ops), one or two shapes
+each; the BatchNorm passes' channel / row layouts and numerical edges are in
+test_bn_oracle_gpu.py.
 
 Tolerances (stated per op): the kernels compute in fp32 (fp32 MFMA = an exact fp32 fmaf
 chain), the oracle in fp64.  Convolutions: max|err| <= 2e-5 * max|ref| (K up to 36*2048);
