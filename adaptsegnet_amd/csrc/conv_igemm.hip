@@ -477,127 +477,157 @@ size_t splitk_slab_bytes(const Plan &pl) {
   return ((size_t)pl.p.splits * pl.p.M * pl.p.N * sizeof(float) + 255) / 256 * 256;
 }
 
-// Row tile of the plan's kernel (the fused BN statistics count one partial per row tile).
-int plan_bm(const Plan &pl) {
-  if (pl.g16) return pl.g16_bm;
-  if (pl.x3r) return pl.mode == MODE_WGRAD ? pl.x3r_bm : 256;
-  if (pl.x3h) return pl.mode == MODE_WGRAD ? pl.x3r_bm : 256;
-  return (pl.bf16 || pl.x3) ? 128 : kCfgBM[pl.cfg];
+// ------------------------------------------------------------------------------------
+// Planner tunables.  Each value is the outcome of a concluded A/B run; the profile
+// file named beside it is the evidence.
+// ------------------------------------------------------------------------------------
+// F32X3 forward / data-gradient products go to the x3h tile only at K >= this (per shape,
+// tools/conv_bench.py: the layer-1 1x1 products with K = 64 / 128 run slower on the 256-row tile —
+// two to four K steps against its prologue and epilogue; the larger products gain 4-12 %, l4.ds
+// forward 854 -> 775 us; the K 256 products on the staged kernel averaged +0.4 % over two boxes,
+// profiles/r6/x3h_min_k_ab.txt)
+constexpr int kX3hMinK = 512;
+// Term-image weight gradients under the default maths run on the side stream beside the main
+// chain's register-staged blocks: the 128-row tile (96 KB LDS, <= 128 VGPRs) leaves a CU room for
+// one of them, the 256-row one (144 KB) does not — except for Cout >= this (DeeplabVGG's fc6 /
+// fc7, whose main chain runs on the term-image kernel too): there the 256-row tile halves the dY
+// re-reads, c4 +0.4 % over three alternating pairs (profiles/r5/x3r_wgrad_bm256_ab.txt).
+// 0: always the 128-row tile under F32X3.
+constexpr int kX3rWgradBm256MinCout = 1024;
+// Split targets (measured on the step, not per shape; tools/ab.sh):
+//  * weight gradients: ~512 blocks (two per CU), rounded down — 384 / 768 / 1024 measured
+//    -3.2 / -2.3 / -2.5 % at c2 and -2.8 / -3.1 / -3.2 % at c3;
+//  * fwd / data-grad: only grids of at most one block per CU (<= 256 tiles) split, to ~512
+//    blocks — one resident block per CU hides no latency (c3 target-domain layer3: +0.6 %
+//    step); splitting grids of up to two blocks per CU measured 2 % slower, a threshold of
+//    129 tiles -0.1 % c2 / -1.2 % c3.
+constexpr int kSplitTarget = 512;
+// F32X3 weight gradients (side stream) split to ~384 blocks (1.5 per CU), not 512: a full
+// 2-per-CU grid of 16-wave blocks holds every CU for a whole split, and the main stream's
+// short BN / split-K kernels then wait for CU slots.  384 measured c2 +2.4 %, c3 +2.6 %
+// (256 / 320 / 448 / 1024: +1.2 / +1.7 / +2.0 / +0.1 % at c2).  Rounding the split count to
+// nearest instead of down measured -0.2..-0.8 % (profiles/r3/x3_wgrad_split_rounding_ab.txt).
+constexpr int kX3WgradTarget = 384;
+// The LDS-DMA bf16 weight gradient (side stream) to ~256 blocks: half the split-K slab
+// traffic of 512, c5 +1.8 % same box (37.30 / 37.30 / 37.29 vs 36.64 / 36.65 / 36.62,
+// tools/dbg/ab_lib.sh).
+constexpr int kG16WgradTarget = 256;
+// The term-image / x3hw weight gradient keeps >= this many K steps per split (set_splits).
+constexpr int kX3rWgradMinKsteps = 32;
+// bf16 forward / data gradients with N >= this on the LDS-DMA kernel: at N = 64 (layer1, D.conv2's
+// stride-2 data gradient) with half the column tile idle, still faster than the register-staged
+// bf16 kernel: l1.conv2 48 -> 40 us, D.conv2 data gradient 204 -> 171, c5 +0.8 %
+// (profiles/r5/g16_min_n64_ab.txt)
+constexpr int kG16MinN = 64;
+// The 256x256x64 two-stage bf16 tile (ADAPTSEG_OPT_G16_WIDE bit 1) from K >= this (512 / 256
+// speed the 1x1 products up alone, -1.3 % conv time, but cost the c5 step 0.3 %:
+// profiles/r6/g16_wide_min_k_ab.txt) ...
+constexpr int kG16WideMinK = 2048;
+// ... and only where its grid holds >= this many tiles (grids of 128-255 tiles split K to ~256
+// blocks, set_splits): per shape l4.conv2 899 -> 1068 TF/s on it, l3.conv2 at c5's source
+// geometry (225 tiles) 691 -> 893, at the c2 geometry (128 tiles) unsplit 712 -> 551
+// (profiles/r6/g16_wide_ab.txt); the c5 step is within +-0.3 % of a 256-tile threshold
+constexpr int kG16WideMinTiles = 128;
+// Grid cap of the vectorised split-K reduce: 512 / 1024 / 8192 measured within +-0.2 % (the
+// block-stride loop covers any cap)
+constexpr int kSplitkMaxBlocks = 8192;
+
+static Tile cfg_tile(int cfg, bool fast) {
+  return {kCfgBM[cfg], kCfgBN[cfg], fast ? fast_bk(cfg) : BK, kCfgThreads[cfg]};
 }
 
-// F32X3 maths with the caller's term images of the activation operand(s) (the _x forms'
-// copies: the three bf16 terms, pixel-interleaved [n][h][w][3][c]): the product moves to the x3r
-// kernel, which reads them by LDS-DMA instead of splitting fp32 rows in-kernel (F32X3_PRESPLIT:
-// it is there already; it then skips its per-call copy).  Re-plans the grid.
-static void x3_terms_flags(Plan &pl) {
-  pl.x3g = pl.x3r = pl.x3ext = true;
-  pl.x3h = false;
-  if (pl.mode == MODE_WGRAD) pl.x3r_bm = pl.p.M >= 256 ? 256 : 128;   // (make_plan's choice; x3h set 128)
-  // weight gradients under the default maths run on the side stream beside the main chain's
-  // register-staged blocks: the 128-row tile (96 KB LDS, <= 128 VGPRs) leaves a CU room for one
-  // of them, the 256-row one (144 KB) does not — except for Cout >= 1024 (DeeplabVGG's fc6 / fc7,
-  // whose main chain runs on the term-image kernel too): there the 256-row tile halves the dY
-  // re-reads, c4 +0.4 % over three alternating pairs (profiles/r5/x3r_wgrad_bm256_ab.txt)
-#ifndef ADAPTSEG_X3R_WGRAD_BM256_MIN_COUT
-#define ADAPTSEG_X3R_WGRAD_BM256_MIN_COUT 1024   // 0: always the 128-row tile under F32X3
-#endif
-  if (pl.mode == MODE_WGRAD && conv_math() == ADAPTSEG_MATH_F32X3 &&
-      !(ADAPTSEG_X3R_WGRAD_BM256_MIN_COUT > 0 && pl.p.M >= ADAPTSEG_X3R_WGRAD_BM256_MIN_COUT))
-    pl.x3r_bm = 128;
-}
-static void x3_terms(Plan &pl) {
-  if (!copies_are_terms() || !pl.fast || !pl.x3 || !pl.x3r_ok || !pl.act_ext) return;
-  if (pl.mode == MODE_WGRAD && !pl.act_ext2) return;
-  x3_terms_flags(pl);
-  set_splits(pl);
-}
-
-// Grid decomposition: tiles, then split K until the grid has ~2 blocks per CU while keeping
-// >= 8 K-steps per split.  Depends on the K step of the chosen kernel (pl.bk).
-void set_splits(Plan &pl) {
-  ConvParams &p = pl.p;
-  if (!pl.fast) pl.s2 = pl.bf16 = pl.x3 = pl.x3g = pl.x3r = pl.x3h = pl.g16 = false;
-  if (!pl.fast && pl.cfg == 8) pl.cfg = 0;  // cfg 8 is built for vector FAST operands only
-  const int bm = plan_bm(pl);
-  const int bn = pl.g16 ? pl.g16_bn : pl.bf16 ? pl.bf16_bn : pl.x3 ? x3_bn(pl.mode) : kCfgBN[pl.cfg];
-  pl.bk = pl.g16 ? pl.g16_bk : pl.bf16 ? 64 : (pl.x3r || pl.x3h) ? kX3rBK : pl.x3 ? kX3BK : pl.fast ? fast_bk(pl.cfg) : BK;
-  if (pl.s2) {  // rows of the largest parity class; K of the largest tap subset; no K split
-    p.M = p.n * ((p.h + 1) / 2) * ((p.w + 1) / 2);
-    p.K = ((p.kh_ + 1) / 2) * ((p.kw_ + 1) / 2) * p.k;
-  } else if (pl.mode == MODE_DGRAD) {
-    p.M = p.n * p.h * p.w;
-    p.K = p.ntaps * p.k;
+// The plan on the term-image kernel (conv_x3r.hpp): 256x128x32, one 8-wave block per CU; the
+// weight gradient's row tile is 256 for Cout >= 256, else 128 — and under the default maths 128
+// below kX3rWgradBm256MinCout.
+static void use_term_tile(Plan &pl) {
+  int bm = 256;
+  if (pl.mode == MODE_WGRAD) {
+    bm = pl.p.M >= 256 ? 256 : 128;
+    if (conv_math() == ADAPTSEG_MATH_F32X3 && !(kX3rWgradBm256MinCout > 0 && pl.p.M >= kX3rWgradBm256MinCout))
+      bm = 128;
   }
-  pl.tiles = (int)(ceil_div(p.M, bm) * ceil_div(p.N, bn));
-  const int nkt = (int)ceil_div(p.K, pl.bk);
-  // Split targets (measured on the step, not per shape; tools/ab.sh):
-  //  * weight gradients: ~512 blocks (two per CU), rounded down — 384 / 768 / 1024 measured
-  //    -3.2 / -2.3 / -2.5 % at c2 and -2.8 / -3.1 / -3.2 % at c3;
-  //  * fwd / data-grad: only grids of at most one block per CU (<= 256 tiles) split, to ~512
-  //    blocks — one resident block per CU hides no latency (c3 target-domain layer3: +0.6 %
-  //    step); splitting grids of up to two blocks per CU measured 2 % slower, a threshold of
-  //    129 tiles -0.1 % c2 / -1.2 % c3.
-  // >= 4 K-steps per split keeps the slab traffic small next to the GEMM.
-  // Rounding: the blocks of a split grid are equal work, so the grid takes (the most blocks any
-  // CU runs) x (one block's K range); tiles * splits must not overshoot a multiple of the CU
-  // count: ceil(512 / 36) = 15 splits puts 3 blocks on 28 CUs (0.2 units) where 14 puts at most
-  // 2 on every CU (0.143) — round down.
-  constexpr int kSplitTarget = 512;
-  // F32X3 weight gradients (side stream) split to ~384 blocks (1.5 per CU), not 512: a full
-  // 2-per-CU grid of 16-wave blocks holds every CU for a whole split, and the main stream's
-  // short BN / split-K kernels then wait for CU slots.  384 measured c2 +2.4 %, c3 +2.6 %
-  // (256 / 320 / 448 / 1024: +1.2 / +1.7 / +2.0 / +0.1 % at c2).  Rounding the split count to
-  // nearest instead of down measured -0.2..-0.8 % (profiles/r3/x3_wgrad_split_rounding_ab.txt).
-#ifndef ADAPTSEG_X3_WGRAD_TARGET
-#define ADAPTSEG_X3_WGRAD_TARGET 384   // (a compile-time knob of experiment builds, EXTRA=-D...)
-#endif
-  // (the environment variable ADAPTSEG_X3_WGRAD_TARGET overrides it, for A/B runs)
-  static const int kX3WgradTarget = env_int("ADAPTSEG_X3_WGRAD_TARGET", ADAPTSEG_X3_WGRAD_TARGET);
-  // The LDS-DMA bf16 weight gradient (side stream) to ~256 blocks: half the split-K slab
-  // traffic of 512, c5 +1.8 % same box (37.30 / 37.30 / 37.29 vs 36.64 / 36.65 / 36.62,
-  // tools/dbg/ab_lib.sh).
-  constexpr int kG16WgradTarget = 256;
-  // (the term-image F32X3 weight gradient picks its own split count below)
-  const int target = (pl.mode == MODE_WGRAD && pl.g16) ? kG16WgradTarget
-                     : (pl.mode == MODE_WGRAD && pl.x3)            ? kX3WgradTarget
-                                                                   : kSplitTarget;
-  // the LDS-DMA bf16 / x3r kernels run one block per CU: split only grids under half the CUs
-  // (the 256x256 bf16 tile, one block per CU: split under 256 tiles, like x3r)
-  const bool g16w = pl.g16 && pl.g16_bm == 256 && pl.g16_bn == 256;
-  const int split_below = pl.mode == MODE_WGRAD ? target : (pl.x3r || pl.x3h || g16w) ? 256 : pl.g16 ? 128 : 257;
-  int splits = 1;
-  if (pl.mode == MODE_WGRAD && (pl.x3r || pl.x3h)) {
-    // one 8-wave block per CU: the grid takes ceil(tiles * s / 256) rounds of 1/s of the K range,
-    // so pick the split count s (<= 256, >= 32 K steps each) with the fewest such units — e.g.
-    // layer4.conv2 (144 tiles of 128 rows): s = 1 leaves 112 CUs idle for the whole launch
-    // (MFMA busy 0.315 in isolation), s = 7 runs 4 rounds of 1/7 (0.57 of the s = 1 time).
-    // (Round 4 capped s at 16: the 1x1 weight gradients, 1-8 tiles over K = 32-131k pixels, then
-    // ran 16-128 blocks on 256 CUs — layer1 at 4-33 TF/s, layer3's 1x1 at 107-112.)
-#ifndef ADAPTSEG_X3R_WGRAD_MIN_KSTEPS
-#define ADAPTSEG_X3R_WGRAD_MIN_KSTEPS 32
-#endif
-    double best = 1e30;
-    for (int s = 1; s <= 256 && (s == 1 || nkt / s >= ADAPTSEG_X3R_WGRAD_MIN_KSTEPS); ++s) {
-      const double t = (double)ceil_div((int64_t)pl.tiles * s, 256) / s;
-      if (t < best * 0.97) {
-        best = t;
-        splits = s;
-      }
-    }
-  } else if (pl.tiles < split_below && !pl.s2) {
-    splits = std::max(1, ((pl.g16 || pl.x3r || pl.x3h) && pl.mode != MODE_WGRAD ? 256 : target) / pl.tiles);
-    splits = std::min(splits, std::max(1, nkt / 4));
-    splits = std::min(splits, 256);
-  }
-  int per = (int)ceil_div(nkt, splits);
-  splits = (int)ceil_div(nkt, per);
-  p.splits = splits;
-  p.ktiles_per_split = per;
-  pl.slab_bytes = splits > 1 ? splitk_slab_bytes(pl) : 0;
-  if (pl.bf16) pl.slab_bytes += bf16_pre_bytes(pl);
-  if (pl.x3) pl.slab_bytes += x3_pre_bytes(pl);
+  pl.family = Family::X3Terms;
+  pl.tile = {bm, 128, kX3rBK, 512};
 }
 
+// F32X3 conv math, for a vector FAST product whose 16-deep K tiles stay inside one tap.
+static void choose_x3(Plan &pl, const adaptseg_conv_desc *d) {
+  const int op = pl.mode;
+  pl.family = Family::X3;
+  pl.cfg = 0;
+  pl.tile = {128, x3_bn(op), kX3BK, x3_threads(op)};
+  // 256x128 tiles with 32-deep steps on pre-split term images (conv_x3r.hpp): a 32-deep
+  // step inside one tap; weight gradients in 16-B channel chunks of both operands
+  pl.terms_ok = op == ADAPTSEG_CONV_FWD        ? d->c % kX3rBK == 0
+                : op == ADAPTSEG_CONV_BWD_DATA ? d->k % kX3rBK == 0
+                                               : d->c % 8 == 0 && d->k % 8 == 0;
+  if (!pl.terms_ok) return;
+  // F32X3_PRESPLIT: every such product on the term-image kernel, the images made per call
+  // unless the caller supplies them; F32X3 (default): on it only when the caller does
+  // (finish_plan: the engine's layer 3-4 conv2 products, whose term images the BN passes write).
+  // Per-call images under F32X3 measured slower for the multi-tap weight gradients (c2 -1.4 %,
+  // profiles/r3/x3r_wgrad_taps_ab.txt); experiments/r3_rejected.patch keeps that build.
+  if (conv_math() == ADAPTSEG_MATH_F32X3_PRESPLIT) {
+    use_term_tile(pl);
+    return;
+  }
+  // F32X3: products on the x3r tiles with the fp32 operands split in-kernel (igemm_x3h_kernel,
+  // igemm_x3hw_kernel), by ADAPTSEG_OPT_X3H bit 1 (forward) / 2 (data gradient) / 4 (weight
+  // gradient); forward / data gradient only at K >= kX3hMinK and not on the stride-2 parity
+  // classes (D.conv2's data gradient 449 -> 523 us).  The weight gradient runs the 128-row tile
+  // (the 256-row one needs two register sets of six float4 beside its 128 accumulators: it spills).
+  const bool wgrad = op == ADAPTSEG_CONV_BWD_WEIGHT;
+  const bool x3h_fd = pl.p.K >= kX3hMinK && !(op == ADAPTSEG_CONV_BWD_DATA && d->stride == 2);
+  if ((x3h_mode() & (1 << op)) && (wgrad || x3h_fd)) {
+    pl.family = Family::X3Rows;
+    pl.tile = {wgrad ? 128 : 256, 128, kX3rBK, 512};
+  }
+}
+
+// bf16 conv math, for a vector FAST product whose K tiles of 64 stay inside one tap.
+static void choose_bf16(Plan &pl, const adaptseg_conv_desc *d) {
+  const int op = pl.mode;
+  const ConvParams &p = pl.p;
+  const bool wgrad = op == ADAPTSEG_CONV_BWD_WEIGHT;
+  pl.family = Family::Bf16;
+  pl.cfg = 0;
+  // 128x256 (8 waves) halves the refetch of the gathered A operand but measured no faster
+  // (c5 27.6 vs 27.7 images/s, per-shape within +-5 %): only with ADAPTSEG_MATH_BF16_WIDE
+  const bool w256 = conv_math() == ADAPTSEG_MATH_BF16_WIDE && !wgrad && p.N >= 256;
+  pl.tile = {128, w256 ? 256 : 128, 64, wgrad ? 256 : 512};
+  // forward / data gradients with N >= kG16MinN on the LDS-DMA kernel (conv_bf16g.hpp): 128x256
+  // tiles when N >= 256 (the activation operand is fetched once per tap), else 256x128; stride-2
+  // data gradients by parity class too
+  if (!wgrad && p.N >= kG16MinN) {
+    pl.family = Family::Bf16Dma;
+    // K step: 64 (one block per CU) for K >= 2048, else 32 (two blocks per CU: one block's
+    // prologue / epilogue overlaps the other's loop on short-K products) — per shape
+    // (tools/conv_bench.py, kernel time): l3.conv2 (K 2304) 706 vs 675 TF/s, l4.conv3 forward
+    // (K 512) 483 vs 625, l4.conv1 data gradient (K 512) 488 vs 631
+    const int bk = (p.K >= 2048 && !pl.s2) ? 64 : 32;   // parity classes: short K, step 32
+    pl.tile = p.N >= 256 ? Tile{128, 256, bk, 512} : Tile{256, 128, bk, 512};
+    // 256x256x64, two stages, 16 waves (kG16WideMinK, kG16WideMinTiles)
+    const int64_t wide_tiles = ceil_div(p.M, 256) * ceil_div(p.N, 256);
+    if ((g16_wide_mode() & 1) && p.N >= 256 && p.K >= kG16WideMinK && !pl.s2 && wide_tiles >= kG16WideMinTiles)
+      pl.tile = {256, 256, 64, 1024};
+    // (256x256x32 tiles, one block per CU, measured slower: c5 -10 % / -2.4 % with the weight
+    // gradients only, profiles/r3/bf16_wide_tiles_ab.txt; experiments/r3_rejected.patch)
+  }
+  // weight gradients with 16-B channel chunks (Cin % 8 == 0, Cout % 8 == 0) on the LDS-DMA
+  // weight-gradient kernel: {128,256}x128 tiles, K steps of 32 output pixels
+  // (its pixel walk keeps 32-bit element offsets: operands of < 2^31 elements, g16_wgrad_fits)
+  const bool g16_wgrad_fits = ((int64_t)p.n * p.oh * p.ow + 64) * p.k < INT32_MAX &&
+                              ((int64_t)p.n + 1) * p.h * p.w * p.c < INT32_MAX;
+  if (wgrad && d->c % 8 == 0 && d->k % 8 == 0 && g16_wgrad_fits) {
+    pl.family = Family::Bf16Dma;
+    pl.tile = {d->k >= 256 ? 256 : 128, 128, 32, 512};   // 256 rows: dY read once per column tile
+    // 256x256 with 64-pixel K steps (16 waves, two stages: ADAPTSEG_OPT_G16_WIDE bit 2)
+    if ((g16_wide_mode() & 2) && d->k >= 256 && p.N >= 256) pl.tile = {256, 256, 64, 1024};
+  }
+}
+
+// Phase 1, choose: the kernel family and tile of the product for 16-B aligned operands and no
+// caller-supplied copies.  finish_plan completes the plan.
 int make_plan(const adaptseg_conv_desc *d, int op, Plan &pl) {
   int st = validate(d);
   if (st) return st;
@@ -606,6 +636,8 @@ int make_plan(const adaptseg_conv_desc *d, int op, Plan &pl) {
   pl.mode = op;
   pl.act_ext = pl.act_ext2 = nullptr;
   pl.wpack_ext = nullptr;
+  pl.tiles = 0;
+  pl.slab_bytes = 0;
   const bool nhwc_in = d->in_stride[1] == 1;
   if (op == ADAPTSEG_CONV_FWD) {
     p.M = d->n * d->oh * d->ow;
@@ -655,15 +687,16 @@ int make_plan(const adaptseg_conv_desc *d, int op, Plan &pl) {
   if (pl.cfg == 0 && op == ADAPTSEG_CONV_FWD) pl.cfg = 8;
   p.fd_nseg_k = make_fastdiv(p.kseg);
   pl.flops = conv_flops(d);
-  // FAST path eligibility (alignment re-checked at launch).  Vector operands need tile-
-  // uniform taps and float4 rows; otherwise the per-element (AE / BE) variants apply.
+  // FAST path eligibility (alignment is finish_plan's).  Vector operands need tile-uniform taps
+  // and float4 rows; otherwise the per-element (AE / BE) variants apply.
   const int fbk = fast_bk(pl.cfg);
+  bool fast;
   pl.s2 = pl.ae = pl.be = false;
   if (op == ADAPTSEG_CONV_FWD) {
     if (nhwc_in && d->c % fbk == 0) {
-      pl.fast = true;
+      fast = true;
     } else {
-      pl.fast = d->nseg == 1;
+      fast = d->nseg == 1;
       pl.ae = true;
       pl.be = p.kseg % 4 != 0 || p.K % fbk != 0;  // vector W rows need no K tail
     }
@@ -671,145 +704,158 @@ int make_plan(const adaptseg_conv_desc *d, int op, Plan &pl) {
     const bool s2 = d->stride == 2 && d->nseg == 1 && d->dil[0] == 1;
     pl.ae = d->k % fbk != 0;
     pl.be = d->c % 4 != 0;
-    pl.fast = d->stride == 1 || (s2 && !pl.ae);
-    pl.s2 = s2 && pl.fast;
+    fast = d->stride == 1 || (s2 && !pl.ae);
+    pl.s2 = s2 && fast;
   } else {
-    pl.fast = true;
+    fast = true;
     pl.ae = d->k % 4 != 0;
     pl.be = !(nhwc_in && d->c % 4 == 0);
   }
-  // bf16 conv math: the vector FAST cases whose K tiles of 64 stay inside one tap
-  pl.bf16 = pl.g16 = false;
-  const bool bf16_math = conv_math() == ADAPTSEG_MATH_BF16 || conv_math() == ADAPTSEG_MATH_BF16_WIDE;
-  if (bf16_math && pl.fast && !pl.ae && !pl.be) {
-    if (op == ADAPTSEG_CONV_FWD) pl.bf16 = d->c % 64 == 0;
-    else if (op == ADAPTSEG_CONV_BWD_DATA) pl.bf16 = d->k % 64 == 0;
-    else pl.bf16 = true;
-  }
-  // F32X3 conv math: the vector FAST cases whose 16-deep K tiles stay inside one tap
-  pl.x3 = pl.x3g = pl.x3r = pl.x3r_ok = pl.x3ext = pl.x3h = false;
-  pl.x3r_bm = 256;
-  const bool x3_math = conv_math() == ADAPTSEG_MATH_F32X3 || conv_math() == ADAPTSEG_MATH_F32X3_PRESPLIT;
-  if (x3_math && pl.fast && !pl.ae && !pl.be) {
-    if (op == ADAPTSEG_CONV_FWD) pl.x3 = d->c % kX3BK == 0;
-    else if (op == ADAPTSEG_CONV_BWD_DATA) pl.x3 = d->k % kX3BK == 0;
-    else pl.x3 = true;
-    // 256x128 tiles with 32-deep steps on pre-split term images (conv_x3r.hpp): a 32-deep
-    // step inside one tap; weight gradients in 16-B channel chunks of both operands
-    if (pl.x3) {
-      if (op == ADAPTSEG_CONV_FWD) pl.x3r_ok = d->c % kX3rBK == 0;
-      else if (op == ADAPTSEG_CONV_BWD_DATA) pl.x3r_ok = d->k % kX3rBK == 0;
-      else pl.x3r_ok = d->c % 8 == 0 && d->k % 8 == 0;
-      if (op == ADAPTSEG_CONV_BWD_WEIGHT) pl.x3r_bm = d->k >= 256 ? 256 : 128;
-    }
-    // F32X3_PRESPLIT: every such product on the term-image kernel, the images made per call
-    // unless the caller supplies them; F32X3 (default): on it only when the caller does (x3_terms:
-    // the engine's layer 3-4 conv2 products, whose term images the BN passes write).  Per-call
-    // images under F32X3 measured slower for the multi-tap weight gradients (c2 -1.4 %,
-    // profiles/r3/x3r_wgrad_taps_ab.txt); experiments/r3_rejected.patch keeps that build.
-    if (pl.x3 && conv_math() == ADAPTSEG_MATH_F32X3_PRESPLIT) pl.x3g = pl.x3r = pl.x3r_ok;
-    // F32X3: products on the x3r tiles with the fp32 operands split in-kernel (igemm_x3h_kernel,
-    // igemm_x3hw_kernel), by ADAPTSEG_X3H bit 1 (forward) / 2 (data gradient) / 4 (weight gradient)
-    // Forward / data gradient only at K >= 512 (256 until late round 6; per shape, tools/conv_bench.py: the layer-1 1x1
-    // products with K = 64 / 128 run slower on the 256-row tile — two to four K steps against its
-    // prologue and epilogue) and not on the stride-2 parity classes (D.conv2's data gradient 449 ->
-    // 523 us); the larger products gain 4-12 % (l4.ds forward 854 -> 775 us).
-    // (round-6 final program: 512 — the K 256 products back on the staged kernel averaged +0.4 %
-    // over 256 on two boxes, profiles/r6/x3h_min_k_ab.txt; ADAPTSEG_X3H_MIN_K for A/B runs)
-    static const int x3h_min_k = env_int("ADAPTSEG_X3H_MIN_K", 512);
-    const bool x3h_fd = p.K >= x3h_min_k && !(op == ADAPTSEG_CONV_BWD_DATA && d->stride == 2);
-    if (pl.x3 && pl.x3r_ok && conv_math() == ADAPTSEG_MATH_F32X3 &&
-        ((op == ADAPTSEG_CONV_FWD && (x3h_mode() & 1) && x3h_fd) ||
-         (op == ADAPTSEG_CONV_BWD_DATA && (x3h_mode() & 2) && x3h_fd) ||
-         (op == ADAPTSEG_CONV_BWD_WEIGHT && (x3h_mode() & 4)))) {
-      pl.x3h = true;
-      if (op == ADAPTSEG_CONV_BWD_WEIGHT) pl.x3r_bm = 128;   // igemm_x3hw_kernel<128> (conv_launch_x3.hip)
-    }
-  }
-  if (pl.x3) pl.cfg = 0;
-  if (pl.bf16) {
-    pl.cfg = 0;
-    // 128x256 (8 waves) halves the refetch of the gathered A operand but measured no faster
-    // (c5 27.6 vs 27.7 images/s, per-shape within +-5 %): only with ADAPTSEG_MATH_BF16_WIDE
-    const bool w256 = conv_math() == ADAPTSEG_MATH_BF16_WIDE;
-    pl.bf16_bn = (w256 && op != ADAPTSEG_CONV_BWD_WEIGHT && p.N >= 256) ? 256 : 128;
-    // forward / data gradients with N >= 64 on the LDS-DMA kernel (conv_bf16g.hpp): 128x256 tiles
-    // when N >= 256 (the activation operand is fetched once per tap), else 256x128 — at N = 64
-    // (layer1, D.conv2's stride-2 data gradient) with half the column tile idle, still faster than
-    // the register-staged bf16 kernel: l1.conv2 48 -> 40 us, D.conv2 data gradient 204 -> 171,
-    // c5 +0.8 % (profiles/r5/g16_min_n64_ab.txt; 128: the round-4 threshold)
-#ifndef ADAPTSEG_G16_MIN_N
-#define ADAPTSEG_G16_MIN_N 64
-#endif
-    if (op != ADAPTSEG_CONV_BWD_WEIGHT && p.N >= ADAPTSEG_G16_MIN_N) {   // stride-2 data gradients by parity class too
-      pl.g16 = true;
-      pl.g16_bm = p.N >= 256 ? 128 : 256;
-      pl.g16_bn = p.N >= 256 ? 256 : 128;
-      // K step: 64 (one block per CU) for K >= 2048, else 32 (two blocks per CU: one block's
-      // prologue / epilogue overlaps the other's loop on short-K products) — per shape
-      // (tools/conv_bench.py, kernel time): l3.conv2 (K 2304) 706 vs 675 TF/s, l4.conv3 forward
-      // (K 512) 483 vs 625, l4.conv1 data gradient (K 512) 488 vs 631
-      pl.g16_bk = (p.K >= 2048 && !pl.s2) ? 64 : 32;   // parity classes: short K, step 32
-      // 256x256x64, two stages (ADAPTSEG_G16_WIDE_MIN_K: the smallest K, for A/B runs; 512 / 256
-      // speed the 1x1 products up alone, -1.3 % conv time, but cost the c5 step 0.3 %:
-      // profiles/r6/g16_wide_min_k_ab.txt)
-      static const int wide_min_k = env_int("ADAPTSEG_G16_WIDE_MIN_K", 2048);
-      // ... and only where its grid holds >= 128 tiles (grids of 128-255 tiles split K to ~256
-      // blocks, set_splits): per shape l4.conv2 899 -> 1068 TF/s on it, l3.conv2 at c5's source
-      // geometry (225 tiles) 691 -> 893, at the c2 geometry (128 tiles) unsplit 712 -> 551
-      // (profiles/r6/g16_wide_ab.txt); the c5 step is within +-0.3 % of a 256-tile threshold
-      static const int wide_min_tiles = env_int("ADAPTSEG_G16_WIDE_MIN_TILES", 128);   // (under 256: split-K to 256 blocks)
-      const int64_t wide_tiles = ceil_div(p.M, 256) * ceil_div(p.N, 256);
-      if ((g16_wide_mode() & 1) && p.N >= 256 && p.K >= wide_min_k && !pl.s2 && wide_tiles >= wide_min_tiles) {
-        pl.g16_bm = 256;
-        pl.g16_bk = 64;
-      }
-      // (256x256x32 tiles, one block per CU, measured slower: c5 -10 % / -2.4 % with the weight
-      // gradients only, profiles/r3/bf16_wide_tiles_ab.txt; experiments/r3_rejected.patch)
-    }
-    // weight gradients with 16-B channel chunks (Cin % 8 == 0, Cout % 8 == 0) on the LDS-DMA
-    // weight-gradient kernel: {128,256}x128 tiles, K steps of 32 output pixels
-    // (its pixel walk keeps 32-bit element offsets: operands of < 2^31 elements, g16_wgrad_fits)
-    const bool g16_wgrad_fits = ((int64_t)p.n * p.oh * p.ow + 64) * p.k < INT32_MAX &&
-                                ((int64_t)p.n + 1) * p.h * p.w * p.c < INT32_MAX;
-    if (op == ADAPTSEG_CONV_BWD_WEIGHT && d->c % 8 == 0 && d->k % 8 == 0 && g16_wgrad_fits) {
-      pl.g16 = true;
-      pl.g16_bm = d->k >= 256 ? 256 : 128;   // 256 rows: dY read once per column tile
-      pl.g16_bn = 128;
-      pl.g16_bk = 32;
-      // 256x256 with 64-pixel K steps (16 waves, two stages: ADAPTSEG_OPT_G16_WIDE)
-      if ((g16_wide_mode() & 2) && d->k >= 256 && p.N >= 256) {
-        pl.g16_bn = 256;
-        pl.g16_bk = 64;
-      }
-    }
+  pl.family = fast ? Family::Fast : Family::Generic;
+  pl.terms_ok = pl.act_caller = false;
+  // the bf16-MFMA maths take the vector FAST products whose K tiles stay inside one tap: a run of
+  // kdim channels per tap (the weight gradient's K is pixels: any)
+  const bool wgrad = op == ADAPTSEG_CONV_BWD_WEIGHT;
+  const int kdim = op == ADAPTSEG_CONV_FWD ? d->c : d->k;
+  const int math = conv_math();
+  if (fast && !pl.ae && !pl.be) {
+    if ((math == ADAPTSEG_MATH_BF16 || math == ADAPTSEG_MATH_BF16_WIDE) && (wgrad || kdim % 64 == 0))
+      choose_bf16(pl, d);
+    if ((math == ADAPTSEG_MATH_F32X3 || math == ADAPTSEG_MATH_F32X3_PRESPLIT) && (wgrad || kdim % kX3BK == 0))
+      choose_x3(pl, d);
   }
   // cfg 8 (occupancy-3 BK-16 tile) exists for vector FAST fwd / weight-grad products only
-  if (pl.cfg == 8 && (!pl.fast || pl.ae || pl.be || pl.s2)) {
+  if (pl.cfg == 8 && (!fast || pl.ae || pl.be || pl.s2)) {
     if (op == ADAPTSEG_CONV_BWD_DATA) {  // screened above: unreachable unless misaligned
       set_error("conv: data-gradient plan on cfg 8 without vector FAST operands");
       return ADAPTSEG_ERR_ARG;
     }
     pl.cfg = 0;
   }
-  set_splits(pl);
+  if (pl.family == Family::Fast || pl.family == Family::Generic) pl.tile = cfg_tile(pl.cfg, fast);
   return ADAPTSEG_OK;
 }
 
+// A misaligned operand: the plan moves to the generic gather kernel, the only one that reads
+// operands per element (cfg 8 is built for vector FAST operands only: its cfg-0 twin).
+static void downgrade_to_generic(Plan &pl) {
+  pl.family = Family::Generic;
+  pl.s2 = false;
+  if (pl.cfg == 8) pl.cfg = 0;
+  pl.tile = cfg_tile(pl.cfg, false);
+}
+
+// Phase 2, finish: the plan for what the caller knows about the operands.  A misaligned fp32
+// operand downgrades it; under the F32X3 maths the caller's term images of the activation
+// operand(s) (the _x forms' copies: the three bf16 terms, pixel-interleaved [n][h][w][3][c]) move an
+// eligible product to the term-image kernel, which reads them by LDS-DMA instead of splitting fp32
+// rows in-kernel (F32X3_PRESPLIT: it is there already; it then skips its per-call copy).
+void finish_plan(Plan &pl, const Operands &ops) {
+  if (!ops.a_aligned) pl.va = false;
+  if (!ops.b_aligned) pl.vb = false;
+  if (!ops.a_aligned || !ops.b_aligned) downgrade_to_generic(pl);
+  if (ops.copies && is_x3(pl.family) && pl.terms_ok) {
+    use_term_tile(pl);
+    pl.act_caller = true;
+  }
+  set_splits(pl);
+}
+
+// Phase 3, split: tiles, then split K until the grid has ~2 blocks per CU while keeping >= 4
+// K-steps per split (the slab traffic stays small next to the GEMM), and the workspace bytes.
+// Reads the plan's family and tile; changes neither.
+// Rounding: the blocks of a split grid are equal work, so the grid takes (the most blocks any
+// CU runs) x (one block's K range); tiles * splits must not overshoot a multiple of the CU
+// count: ceil(512 / 36) = 15 splits puts 3 blocks on 28 CUs (0.2 units) where 14 puts at most
+// 2 on every CU (0.143) — round down.
+void set_splits(Plan &pl) {
+  ConvParams &p = pl.p;
+  const Tile &t = pl.tile;
+  const bool wgrad = pl.mode == MODE_WGRAD;
+  const bool dma = pl.family == Family::Bf16Dma;
+  const bool one_per_cu = pl.family == Family::X3Terms || pl.family == Family::X3Rows;   // 8-wave 256x128x32 blocks
+  if (pl.s2) {  // rows of the largest parity class; K of the largest tap subset; no K split
+    p.M = p.n * ((p.h + 1) / 2) * ((p.w + 1) / 2);
+    p.K = ((p.kh_ + 1) / 2) * ((p.kw_ + 1) / 2) * p.k;
+  } else if (pl.mode == MODE_DGRAD) {
+    p.M = p.n * p.h * p.w;
+    p.K = p.ntaps * p.k;
+  }
+  pl.tiles = (int)(ceil_div(p.M, t.bm) * ceil_div(p.N, t.bn));
+  const int nkt = (int)ceil_div(p.K, t.bk);
+  // (the term-image F32X3 weight gradient picks its own split count below)
+  const int target = (wgrad && dma) ? kG16WgradTarget : (wgrad && is_x3(pl.family)) ? kX3WgradTarget : kSplitTarget;
+  // the LDS-DMA bf16 / x3r kernels run one block per CU: split only grids under half the CUs
+  // (the 256x256 bf16 tile, one block per CU: split under 256 tiles, like x3r)
+  const bool g16w = dma && t.bm == 256 && t.bn == 256;
+  const int split_below = wgrad ? target : (one_per_cu || g16w) ? 256 : dma ? 128 : 257;
+  int splits = 1;
+  if (wgrad && one_per_cu) {
+    // one 8-wave block per CU: the grid takes ceil(tiles * s / 256) rounds of 1/s of the K range,
+    // so pick the split count s (<= 256, >= kX3rWgradMinKsteps K steps each) with the fewest such
+    // units — e.g. layer4.conv2 (144 tiles of 128 rows): s = 1 leaves 112 CUs idle for the whole
+    // launch (MFMA busy 0.315 in isolation), s = 7 runs 4 rounds of 1/7 (0.57 of the s = 1 time).
+    // (A cap of 16 splits left the 1x1 weight gradients, 1-8 tiles over K = 32-131k pixels, on
+    // 16-128 blocks of 256 CUs — layer1 at 4-33 TF/s, layer3's 1x1 at 107-112.)
+    double best = 1e30;
+    for (int s = 1; s <= 256 && (s == 1 || nkt / s >= kX3rWgradMinKsteps); ++s) {
+      const double u = (double)ceil_div((int64_t)pl.tiles * s, 256) / s;
+      if (u < best * 0.97) {
+        best = u;
+        splits = s;
+      }
+    }
+  } else if (pl.tiles < split_below && !pl.s2) {
+    splits = std::max(1, ((dma || one_per_cu) && !wgrad ? 256 : target) / pl.tiles);
+    splits = std::min(splits, std::max(1, nkt / 4));
+    splits = std::min(splits, 256);
+  }
+  int per = (int)ceil_div(nkt, splits);
+  splits = (int)ceil_div(nkt, per);
+  p.splits = splits;
+  p.ktiles_per_split = per;
+  pl.slab_bytes = splits > 1 ? splitk_slab_bytes(pl) : 0;
+  if (is_bf16(pl.family)) pl.slab_bytes += bf16_pre_bytes(pl);
+  if (is_x3(pl.family)) pl.slab_bytes += x3_pre_bytes(pl);
+}
+
+// The selector table: (family, weight-gradient or not, tile, stride-2 parity form) -> the
+// selector's last two digits; kernel_id adds 100 * mode.  The first matching row counts.  The
+// table in include/adaptseg.h ("Kernel selectors") is written from this one.  Some rows reuse
+// ids of Fast cfg-8 variants that do not exist (cfg 8 takes vector stride-1 operands only: 85-89).
+struct SelectorRow {
+  Family family;
+  int wgrad;        // 1: the weight-gradient kernel, 0: forward / data gradient, -1: any
+  int bm, bn, bk;   // 0: any
+  bool s2;
+  int id;
+};
+static const SelectorRow kSelectors[] = {
+    {Family::Bf16Dma, 1, 256, 256, 64, false, 85}, {Family::Bf16Dma, 1, 256, 128, 32, false, 98},
+    {Family::Bf16Dma, 1, 128, 128, 32, false, 99},
+    {Family::Bf16Dma, 0, 128, 256, 32, true, 92},  {Family::Bf16Dma, 0, 256, 128, 32, true, 93},
+    {Family::Bf16Dma, 0, 256, 256, 64, false, 85}, {Family::Bf16Dma, 0, 128, 256, 64, false, 97},
+    {Family::Bf16Dma, 0, 256, 128, 64, false, 98}, {Family::Bf16Dma, 0, 128, 256, 32, false, 94},
+    {Family::Bf16Dma, 0, 256, 128, 32, false, 99},
+    {Family::X3Rows, 0, 256, 128, 32, false, 86},  {Family::X3Rows, 0, 256, 128, 32, true, 87},
+    {Family::X3Rows, 1, 256, 128, 32, false, 86},  {Family::X3Rows, 1, 128, 128, 32, false, 87},
+    {Family::X3Terms, 0, 256, 128, 32, false, 88}, {Family::X3Terms, 0, 256, 128, 32, true, 89},
+    {Family::X3Terms, 1, 256, 128, 32, false, 88}, {Family::X3Terms, 1, 128, 128, 32, false, 89},
+    {Family::Bf16, -1, 128, 128, 64, false, 90},   {Family::Bf16, -1, 128, 128, 64, true, 91},
+    {Family::Bf16, -1, 128, 256, 64, false, 92},   {Family::Bf16, -1, 128, 256, 64, true, 93},
+    {Family::X3, -1, 128, 128, 16, false, 95},     {Family::X3, -1, 128, 128, 16, true, 96},
+};
+
 int kernel_id(const Plan &pl, int mode) {
-  // 88 / 89: the FAST cfg-8 stride-2 ids, which never occur (cfg 8 has no stride-2 form)
-  if (pl.x3r) return 100 * mode + 88 + ((mode == MODE_WGRAD ? pl.x3r_bm == 128 : pl.s2) ? 1 : 0);
-  // 86 / 87: the FAST cfg-8 per-element ids, which never occur (cfg 8 takes vector operands only)
-  if (pl.x3h) return 100 * mode + 86 + ((mode == MODE_WGRAD ? pl.x3r_bm == 128 : pl.s2) ? 1 : 0);
-  if (pl.g16 && mode == MODE_WGRAD) return 100 * mode + (pl.g16_bn == 256 ? 85 : pl.g16_bm == 256 ? 98 : 99);
-  if (pl.g16 && pl.s2) return 100 * mode + (pl.g16_bn == 256 ? 92 : 93);
-  // 85: the FAST cfg-8 id with per-element B, which never occurs (cfg 8: vector operands only)
-  if (pl.g16 && pl.g16_bm == 256 && pl.g16_bn == 256) return 100 * mode + 85;
-  if (pl.g16) return 100 * mode + (pl.g16_bk == 64 ? (pl.g16_bn == 256 ? 97 : 98) : (pl.g16_bn == 256 ? 94 : 99));
-  if (pl.bf16) return 100 * mode + 90 + (pl.s2 ? 1 : 0) + (pl.bf16_bn == 256 ? 2 : 0);
-  if (pl.x3) return 100 * mode + 95 + (pl.s2 ? 1 : 0);
-  // FAST: 4 + (S2 ? 4 : 0) + (AE ? 2 : 0) + (BE ? 1 : 0)  ->  4..11 (S2 variants 8, 9)
-  if (pl.fast) return 100 * mode + 10 * pl.cfg + 4 + (pl.s2 ? 4 : 0) + (pl.ae ? 2 : 0) + (pl.be ? 1 : 0);
+  const Tile &t = pl.tile;
+  for (const SelectorRow &r : kSelectors)
+    if (r.family == pl.family && (r.wgrad < 0 || r.wgrad == (mode == MODE_WGRAD)) && r.bm == t.bm && r.bn == t.bn &&
+        r.bk == t.bk && r.s2 == pl.s2)
+      return 100 * mode + r.id;
+  // Fast: 10 * cfg + 4 + (S2 ? 4 : 0) + (AE ? 2 : 0) + (BE ? 1 : 0)  ->  4..11 (S2 variants 8, 9)
+  if (pl.family == Family::Fast)
+    return 100 * mode + 10 * pl.cfg + 4 + (pl.s2 ? 4 : 0) + (pl.ae ? 2 : 0) + (pl.be ? 1 : 0);
+  // Generic: 10 * cfg + (vector A ? 2 : 0) + (vector B ? 1 : 0)
   return 100 * mode + 10 * pl.cfg + (pl.va ? 2 : 0) + (pl.vb ? 1 : 0);
 }
 
@@ -847,10 +893,7 @@ static int splitk_sum(const ConvParams &q, const float *slab, int mode, hipStrea
   if (vec) {
     const FastDiv fdn4 = make_fastdiv((uint32_t)q.N / 4);
     const int G = q.splits >= 64 ? 16 : q.splits >= 16 ? 4 : 1;
-    // grid cap: 512 / 1024 / 8192 measured within +-0.2 % (round 3); ADAPTSEG_SPLITK_MAX_BLOCKS
-    // for A/B runs (the block-stride loop covers any cap)
-    static const int max_blocks = env_int("ADAPTSEG_SPLITK_MAX_BLOCKS", 8192);
-    const int blocks = (int)std::min<size_t>(ceil_div(total / 4, 256 / G), (size_t)std::max(1, max_blocks));
+    const int blocks = (int)std::min<size_t>(ceil_div(total / 4, 256 / G), (size_t)kSplitkMaxBlocks);
     if (G == 16) splitk_reduce4_kernel<16><<<blocks, 256, 0, s>>>(q, slab, mode, fdn4);
     else if (G == 4) splitk_reduce4_kernel<4><<<blocks, 256, 0, s>>>(q, slab, mode, fdn4);
     else splitk_reduce4_kernel<1><<<blocks, 256, 0, s>>>(q, slab, mode, fdn4);
@@ -886,7 +929,8 @@ int run_plan(Plan &pl, int mode, void *ws, size_t ws_bytes, hipStream_t s, bool 
     }
   }
   // workspace: [weight pack / operand copies (F32X3, bf16)][split-K slabs][tile counters]
-  const size_t pre = pl.x3 ? x3_pre_bytes(pl) : pl.bf16 ? bf16_pre_bytes(pl) : 0;
+  const bool x3 = is_x3(pl.family), bf16 = is_bf16(pl.family);
+  const size_t pre = x3 ? x3_pre_bytes(pl) : bf16 ? bf16_pre_bytes(pl) : 0;
   float *slab = nullptr;
   if (pl.p.splits > 1) {
     slab = reinterpret_cast<float *>(reinterpret_cast<char *>(ws) + pre);
@@ -894,13 +938,13 @@ int run_plan(Plan &pl, int mode, void *ws, size_t ws_bytes, hipStream_t s, bool 
   }
   hipError_t e;
   int slot;
-  if (pl.bf16 || pl.x3) {
+  if (bf16 || x3) {
     // weight pack (+ operand copies) first, outside the timed bracket: the live roofline
     // times the GEMM kernel alone, as rocprof reports it
-    e = pl.x3 ? prep_x3(pl, ws, s) : prep_bf16(pl, ws, s);
+    e = x3 ? prep_x3(pl, ws, s) : prep_bf16(pl, ws, s);
     if (e == hipSuccess) {
       timing_begin_exec(kernel_id(pl, mode), s, pl.flops, &slot);
-      e = pl.x3 ? launch_x3(pl, ws, s) : launch_bf16(pl, ws, s);
+      e = x3 ? launch_x3(pl, ws, s) : launch_bf16(pl, ws, s);
       timing_end(slot, s);
     }
   } else {
@@ -967,7 +1011,7 @@ __global__ void __launch_bounds__(256) x3_out_copy4_kernel(const float4 *__restr
 // kernels: the staged and term-image ones) instead of by out_copy's pass over the finished fp32
 // output: 8-B aligned images, N % 4 == 0, < 2^31 term elements (the epilogue's 32-bit offsets)
 static bool terms_in_epilogue(const Plan &pl, const uint16_t *yb, int64_t n) {
-  return yb && pl.fast && pl.x3 && pl.p.N % 4 == 0 && 3 * n < (1ll << 31) && !(reinterpret_cast<uintptr_t>(yb) & 7);
+  return yb && is_x3(pl.family) && pl.p.N % 4 == 0 && 3 * n < (1ll << 31) && !(reinterpret_cast<uintptr_t>(yb) & 7);
 }
 
 // The operand copy of a finished output [n / C][C] (the paths whose kernels do not write it): a
@@ -998,15 +1042,15 @@ bool use_thin(const adaptseg_conv_desc *d, int op) { return thin_eligible(d, op)
 static bool copy_only(const Plan &pl, const adaptseg_conv_desc *d, int op) {
   if (use_thin(d, op)) return false;
   if (tapgemm_eligible(d)) return tapgemm_copy_only(d, op);
-  if (copies_are_terms()) return pl.fast && pl.x3 && pl.x3r_ok;   // x3r on the caller's terms
-  return pl.g16 || (pl.bf16 && op == ADAPTSEG_CONV_FWD);
+  if (is_x3(pl.family)) return pl.terms_ok;   // the term-image kernel on the caller's terms
+  return pl.family == Family::Bf16Dma || (pl.family == Family::Bf16 && op == ADAPTSEG_CONV_FWD);
 }
 
 // Bytes of the weight pack the plan's kernel reads (0: none).
 static size_t plan_wpack_bytes(const Plan &pl) {
   if (pl.mode == MODE_WGRAD) return 0;
-  if (pl.x3) return x3_wpack_bytes(pl);
-  if (pl.bf16) return bf16_wpack_bytes(pl);
+  if (is_x3(pl.family)) return x3_wpack_bytes(pl);
+  if (is_bf16(pl.family)) return bf16_wpack_bytes(pl);
   return 0;
 }
 
@@ -1020,6 +1064,24 @@ static int attach_wpack(Plan &pl, const void *w_pack) {
   return ADAPTSEG_OK;
 }
 
+// finish_plan for the launch paths, from their pointers: the fp32 operands' alignment, and the
+// caller's activation copies where every copy the product reads is there and 16-B aligned (the
+// weight gradient reads two, of dY and of x: both or none).
+static void finish_plan(Plan &pl, bool a_aligned, bool b_aligned, const void *act, const void *act2 = nullptr) {
+  const bool two = pl.mode == MODE_WGRAD;
+  const bool have = act && aligned16(act) && (!two || (act2 && aligned16(act2)));
+  finish_plan(pl, Operands{a_aligned, b_aligned, have});
+  pl.act_ext = have ? act : nullptr;
+  pl.act_ext2 = have && two ? act2 : nullptr;
+}
+
+// make_plan + finish_plan for a host query
+static int query_plan(const adaptseg_conv_desc *d, int op, const Operands &ops, Plan &pl) {
+  const int st = make_plan(d, op, pl);
+  if (st == ADAPTSEG_OK) finish_plan(pl, ops);
+  return st;
+}
+
 }  // namespace adaptseg
 
 using namespace adaptseg;
@@ -1028,21 +1090,16 @@ extern "C" {
 
 int adaptseg_conv2d_workspace_size(const adaptseg_conv_desc *d, int op, size_t *bytes) {
   AS_CHECK_ARG(bytes, "null bytes");
-  Plan pl;
-  int st = make_plan(d, op, pl);
+  Plan base, pl;
+  int st = make_plan(d, op, base);
   if (st) return st;
-  size_t b = pl.slab_bytes;
-  if (pl.fast) {  // an unaligned operand at launch time falls back to the generic kernel
-    Plan g = pl;
-    g.fast = false;
-    set_splits(g);
-    b = std::max(b, g.slab_bytes);
-  }
-  if (pl.x3r_ok && copies_are_terms()) {   // the plan with the caller's term images
-    Plan t = pl;
-    x3_terms_flags(t);
-    set_splits(t);
-    b = std::max(b, t.slab_bytes);
+  // the largest need of the plans a launch can end on: aligned operands, a misaligned one (the
+  // generic kernel), the caller's term images
+  size_t b = 0;
+  for (const Operands &ops : {Operands{}, Operands{false, false, false}, Operands{true, true, true}}) {
+    pl = base;
+    finish_plan(pl, ops);
+    b = std::max(b, pl.slab_bytes);
   }
   if (tapgemm_eligible(d)) b = std::max(b, tapgemm_workspace(d, op));
   if (use_thin(d, op)) b = std::max(b, thin_workspace(d, op));
@@ -1058,10 +1115,15 @@ int adaptseg_conv2d_workspace_size(const adaptseg_conv_desc *d, int op, size_t *
 
 int adaptseg_conv2d_kernel_id(const adaptseg_conv_desc *d, int op, int *kernel_id, int *splits) {
   AS_CHECK_ARG(kernel_id && splits, "conv2d_kernel_id: null");
+  return adaptseg_conv2d_kernel_id_x(d, op, 0, kernel_id, splits);
+}
+
+int adaptseg_conv2d_kernel_id_x(const adaptseg_conv_desc *d, int op, int with_copies, int *kernel_id, int *splits) {
+  AS_CHECK_ARG(kernel_id && splits, "conv2d_kernel_id_x: null");
   Plan pl;
-  int st = make_plan(d, op, pl);
-  if (st) return st;
   // alignment-dependent downgrades are not known here; report the aligned choice
+  int st = query_plan(d, op, Operands{true, true, with_copies != 0}, pl);
+  if (st) return st;
   if (use_thin(d, op)) {
     *kernel_id = thin_kernel_id(op);
     *splits = 1;
@@ -1073,36 +1135,21 @@ int adaptseg_conv2d_kernel_id(const adaptseg_conv_desc *d, int op, int *kernel_i
   return ADAPTSEG_OK;
 }
 
-int adaptseg_conv2d_kernel_id_x(const adaptseg_conv_desc *d, int op, int with_copies, int *kernel_id, int *splits) {
-  AS_CHECK_ARG(kernel_id && splits, "conv2d_kernel_id_x: null");
-  if (!with_copies || use_thin(d, op) || tapgemm_eligible(d)) return adaptseg_conv2d_kernel_id(d, op, kernel_id, splits);
-  Plan pl;
-  int st = make_plan(d, op, pl);
-  if (st) return st;
-  pl.act_ext = pl.act_ext2 = d;   // any non-NULL: the plan with the caller's operand copies
-  x3_terms(pl);
-  *kernel_id = ::adaptseg::kernel_id(pl, op);
-  *splits = pl.p.splits;
-  return ADAPTSEG_OK;
-}
-
-// The products with an operand-BN kernel (adaptseg_operand_bn): the x3h forward (selector 86)
-// and the register-staged F32X3 weight gradient (295), on a BN of at most kAbnMaxC channels
+// The products with an operand-BN kernel (adaptseg_operand_bn): the x3h forward and the
+// register-staged F32X3 weight gradient, on a BN of at most kAbnMaxC channels
 static bool abn_plan_ok(const Plan &pl, const adaptseg_conv_desc *d, int op) {
   if (d->c > kAbnMaxC || d->c % 4 || d->nseg != 1 || use_thin(d, op) || tapgemm_eligible(d)) return false;
-  const int kid = ::adaptseg::kernel_id(pl, op);
-  return (op == ADAPTSEG_CONV_FWD && kid == 86) || (op == ADAPTSEG_CONV_BWD_WEIGHT && kid == 295);
+  return (op == ADAPTSEG_CONV_FWD && pl.family == Family::X3Rows) ||
+         (op == ADAPTSEG_CONV_BWD_WEIGHT && pl.family == Family::X3);
 }
 
 int adaptseg_conv2d_operand_bn_ok(const adaptseg_conv_desc *d, int op, int *ok) {
   AS_CHECK_ARG(ok, "conv2d_operand_bn_ok: null");
   *ok = 0;
   Plan pl;
-  int st = make_plan(d, op, pl);
+  int st = query_plan(d, op, Operands{}, pl);
   if (st) return st;
   if (op != ADAPTSEG_CONV_FWD && op != ADAPTSEG_CONV_BWD_WEIGHT) return ADAPTSEG_OK;
-  set_splits(pl);
-  x3_terms(pl);
   *ok = abn_plan_ok(pl, d, op) ? 1 : 0;
   return ADAPTSEG_OK;
 }
@@ -1152,7 +1199,7 @@ int adaptseg_conv2d_wpack(const adaptseg_conv_desc *d, int op, const float *cons
     AS_CHECK_ARG(aligned16(w[s]), "conv2d_wpack: weight %d must be 16-byte aligned", s);
     pl.p.wt[s] = w[s];
   }
-  const hipError_t e = pl.x3 ? prep_x3_wpack(pl, pack, as_stream(stream)) : prep_bf16_wpack(pl, pack, as_stream(stream));
+  const hipError_t e = is_x3(pl.family) ? prep_x3_wpack(pl, pack, as_stream(stream)) : prep_bf16_wpack(pl, pack, as_stream(stream));
   if (e != hipSuccess) {
     set_error("conv2d_wpack: %s", hipGetErrorString(e));
     return ADAPTSEG_ERR_HIP;
@@ -1166,26 +1213,44 @@ int adaptseg_conv2d_fwd(const adaptseg_conv_desc *d, const float *x, const float
   return adaptseg_conv2d_fwd_x(d, x, nullptr, w, nullptr, bias, res, y, nullptr, flags, ws, ws_bytes, stream);
 }
 
-int adaptseg_conv2d_fwd_x(const adaptseg_conv_desc *d, const float *x, const uint16_t *x_bf16,
-                          const float *const *w, const void *w_pack, const float *const *bias, const float *res,
-                          float *y, uint16_t *y_bf16, int flags, void *ws, size_t ws_bytes,
-                          adaptseg_stream_t stream) {
+// What the forward writes beside y when the caller asks for the fused BN statistics
+// (adaptseg_conv2d_fwd_bnstats*): the row tiles' partials, and optionally an operand BN on x
+struct FwdStats {
+  float *stats;
+  size_t stats_bytes;
+  int *ntiles;
+  const adaptseg_operand_bn *abn;
+};
+
+// The forward of every entry point; bn: the fused BN statistics form (no bias / residual /
+// activation, never the thin path; the tap-GEMM path has no fused statistics)
+static int fwd_impl(const adaptseg_conv_desc *d, const float *x, const uint16_t *x_bf16, const float *const *w,
+                    const void *w_pack, const float *const *bias, const float *res, float *y, uint16_t *y_bf16,
+                    int flags, void *ws, size_t ws_bytes, adaptseg_stream_t stream, const FwdStats *bn) {
+  const char *who = bn ? "conv fwd_bnstats" : "conv fwd";
+  if (bn) {
+    AS_CHECK_ARG(bn->ntiles && bn->stats, "conv fwd_bnstats: null stats / ntiles");
+    *bn->ntiles = 0;
+  }
   Plan pl;
   int st = make_plan(d, ADAPTSEG_CONV_FWD, pl);
   if (st) return st;
-  AS_CHECK_ARG((x || x_bf16) && w && (y || y_bf16), "conv fwd: null pointer");
-  AS_CHECK_ARG(y || !(use_thin(d, ADAPTSEG_CONV_FWD) || tapgemm_eligible(d)),
-               "conv fwd: this product needs the fp32 output (thin / tap-GEMM path)");
+  const bool thin = !bn && use_thin(d, ADAPTSEG_CONV_FWD);
+  AS_CHECK_ARG((x || x_bf16) && w && (y || y_bf16), "%s: null pointer", who);
+  AS_CHECK_ARG(y || !(thin || tapgemm_eligible(d)), "%s: this product needs the fp32 output%s", who,
+               bn ? "" : " (thin / tap-GEMM path)");
   AS_CHECK_ARG(y || !(flags & ADAPTSEG_EPI_ACCUMULATE), "conv fwd: ACCUMULATE needs the fp32 output");
-  AS_CHECK_ARG(x || (copy_only(pl, d, ADAPTSEG_CONV_FWD) && x_bf16),
-               "conv fwd: this product needs the fp32 input (no bf16-operand kernel for it)");
+  AS_CHECK_ARG(x || copy_only(pl, d, ADAPTSEG_CONV_FWD),
+               "%s: this product needs the fp32 input (no bf16-operand kernel for it)", who);
   AS_CHECK_ARG(!(flags & kEpiActGrad), "conv fwd: *_GRAD flags not valid");
   AS_CHECK_ARG(!((flags & ADAPTSEG_EPI_LEAKY) && (flags & ADAPTSEG_EPI_RELU)), "conv fwd: LEAKY and RELU");
   AS_CHECK_ARG(!(flags & ADAPTSEG_EPI_RESIDUAL) || res, "conv fwd: residual flag without res");
-  for (int s = 0; s < d->nseg; ++s) AS_CHECK_ARG(w[s], "conv fwd: null weight %d", s);
+  for (int s = 0; s < d->nseg; ++s) AS_CHECK_ARG(w[s], "%s: null weight %d", who, s);
+  AS_CHECK_ARG(!bn || !bn->abn || !tapgemm_eligible(d), "conv fwd_bnstats_abn: no operand-BN kernel for this product");
+  if (bn && tapgemm_eligible(d))  // the tap-GEMM path has no fused statistics: plain forward
+    return fwd_impl(d, x, x_bf16, w, nullptr, nullptr, nullptr, y, y_bf16, 0, ws, ws_bytes, stream, nullptr);
   const int64_t ny = (int64_t)d->n * d->oh * d->ow * d->k;
-  if (use_thin(d, ADAPTSEG_CONV_FWD) &&
-      thin_fwd(d, x, w[0], bias ? bias[0] : nullptr, res, y, flags, as_stream(stream)) == ADAPTSEG_OK)
+  if (thin && thin_fwd(d, x, w[0], bias ? bias[0] : nullptr, res, y, flags, as_stream(stream)) == ADAPTSEG_OK)
     return out_copy(y, y_bf16, ny, d->k, as_stream(stream));
   if (tapgemm_eligible(d) && aligned16(x) && segs_aligned(w, d->nseg)) {
     st = tapgemm_fwd(d, x, x_bf16, w, bias, res, y, flags, ws, ws_bytes, as_stream(stream));
@@ -1194,31 +1259,47 @@ int adaptseg_conv2d_fwd_x(const adaptseg_conv_desc *d, const float *x, const uin
   ConvParams &p = pl.p;
   p.x = x;
   for (int s = 0; s < d->nseg; ++s) {
-    AS_CHECK_ARG(w[s], "conv fwd: null weight %d", s);
     p.wt[s] = w[s];
     p.bias[s] = bias ? bias[s] : nullptr;
-    if (reinterpret_cast<uintptr_t>(w[s]) & 15) pl.vb = pl.fast = false;
   }
-  if (reinterpret_cast<uintptr_t>(x) & 15) pl.va = pl.fast = false;
-  set_splits(pl);
-  pl.act_ext = aligned16(x_bf16) ? x_bf16 : nullptr;
-  x3_terms(pl);
-  // a misaligned weight clears pl.fast and, in set_splits, the bf16-operand kernel: only that
-  // kernel reads the copy, so a NULL x needs it to survive the alignment checks too
+  finish_plan(pl, aligned16(x), segs_aligned(w, d->nseg), x_bf16);
+  // a misaligned weight downgrades the plan off the bf16-operand kernel: only that kernel reads
+  // the copy, so a NULL x needs it to survive the alignment checks too
   AS_CHECK_ARG(x || (copy_only(pl, d, ADAPTSEG_CONV_FWD) && pl.act_ext),
-               "conv fwd: x is NULL but the plan (after the alignment checks) needs the fp32 input");
+               "%s: x is NULL but the plan (after the alignment checks) needs the fp32 input", who);
+  if (bn && bn->abn) {
+    AS_CHECK_ARG(abn_plan_ok(pl, d, ADAPTSEG_CONV_FWD),
+                 "conv fwd_bnstats_abn: no operand-BN kernel for this product (adaptseg_conv2d_operand_bn_ok)");
+    set_abn(p, bn->abn);
+  }
   const bool terms = copies_are_terms();   // F32X3: term images of y (the epilogue's, or a pass after the GEMM)
-  AS_CHECK_ARG(y || !terms, "conv fwd: under the F32X3 maths the output is fp32 (y_bf16 is its term images)");
+  AS_CHECK_ARG(y || !terms, "%s: under the F32X3 maths the output is fp32%s", who,
+               bn ? "" : " (y_bf16 is its term images)");
   const bool fused = terms && terms_in_epilogue(pl, y_bf16, ny);
   p.out = y;
   p.outb = (terms && !fused) ? nullptr : reinterpret_cast<__bf16 *>(y_bf16);
   p.outb_terms = fused ? 1 : 0;
   p.res = res;
   p.flags = flags;
+  if (bn && pl.family != Family::Generic && p.splits == 1) {
+    const int nt = (int)ceil_div(p.M, pl.tile.bm);
+    if ((size_t)(nt + 2 * (int64_t)p.N * nt) * sizeof(float) <= bn->stats_bytes) {
+      p.stats = bn->stats;
+      p.stats_ntiles = nt;
+      *bn->ntiles = nt;
+    }
+  }
   st = attach_wpack(pl, w_pack);
   if (st) return st;
   st = run_plan(pl, MODE_FWD, ws, ws_bytes, as_stream(stream));
   return (st || !terms || fused) ? st : out_copy(y, y_bf16, ny, d->k, as_stream(stream));
+}
+
+int adaptseg_conv2d_fwd_x(const adaptseg_conv_desc *d, const float *x, const uint16_t *x_bf16,
+                          const float *const *w, const void *w_pack, const float *const *bias, const float *res,
+                          float *y, uint16_t *y_bf16, int flags, void *ws, size_t ws_bytes,
+                          adaptseg_stream_t stream) {
+  return fwd_impl(d, x, x_bf16, w, w_pack, bias, res, y, y_bf16, flags, ws, ws_bytes, stream, nullptr);
 }
 
 int adaptseg_conv2d_bnstats_size(const adaptseg_conv_desc *d, size_t *bytes) {
@@ -1240,15 +1321,10 @@ int adaptseg_conv2d_bnstats_tiles_x(const adaptseg_conv_desc *d, int with_copy, 
   AS_CHECK_ARG(ntiles, "conv2d_bnstats_tiles: null");
   *ntiles = 0;
   Plan pl;
-  int st = make_plan(d, ADAPTSEG_CONV_FWD, pl);
+  int st = query_plan(d, ADAPTSEG_CONV_FWD, Operands{true, true, with_copy != 0}, pl);
   if (st) return st;
   if (tapgemm_eligible(d)) return ADAPTSEG_OK;
-  if (with_copy) {
-    pl.act_ext = d;   // any non-NULL: the plan with the caller's copy of x
-    x3_terms(pl);
-  }
-  if (pl.fast && pl.p.splits == 1)
-    *ntiles = (int)ceil_div(pl.p.M, plan_bm(pl));
+  if (pl.family != Family::Generic && pl.p.splits == 1) *ntiles = (int)ceil_div(pl.p.M, pl.tile.bm);
   return ADAPTSEG_OK;
 }
 
@@ -1259,17 +1335,12 @@ int adaptseg_conv2d_fwd_bnstats(const adaptseg_conv_desc *d, const float *x, con
                                        stream);
 }
 
-static int fwd_bnstats_impl(const adaptseg_conv_desc *d, const float *x, const uint16_t *x_bf16,
-                            const float *const *w, const void *w_pack, float *y, uint16_t *y_bf16, float *stats,
-                            size_t stats_bytes, int *ntiles, void *ws, size_t ws_bytes, adaptseg_stream_t stream,
-                            const adaptseg_operand_bn *abn);
-
 int adaptseg_conv2d_fwd_bnstats_x(const adaptseg_conv_desc *d, const float *x, const uint16_t *x_bf16,
                                   const float *const *w, const void *w_pack, float *y, uint16_t *y_bf16,
                                   float *stats, size_t stats_bytes, int *ntiles, void *ws, size_t ws_bytes,
                                   adaptseg_stream_t stream) {
-  return fwd_bnstats_impl(d, x, x_bf16, w, w_pack, y, y_bf16, stats, stats_bytes, ntiles, ws, ws_bytes, stream,
-                          nullptr);
+  const FwdStats bn{stats, stats_bytes, ntiles, nullptr};
+  return fwd_impl(d, x, x_bf16, w, w_pack, nullptr, nullptr, y, y_bf16, 0, ws, ws_bytes, stream, &bn);
 }
 
 int adaptseg_conv2d_fwd_bnstats_abn(const adaptseg_conv_desc *d, const float *x_pre, const adaptseg_operand_bn *abn,
@@ -1277,64 +1348,8 @@ int adaptseg_conv2d_fwd_bnstats_abn(const adaptseg_conv_desc *d, const float *x_
                                     size_t stats_bytes, int *ntiles, void *ws, size_t ws_bytes,
                                     adaptseg_stream_t stream) {
   AS_CHECK_ARG(abn && abn->mean && abn->invstd && x_pre, "conv fwd_bnstats_abn: null operand BN / input");
-  return fwd_bnstats_impl(d, x_pre, nullptr, w, w_pack, y, nullptr, stats, stats_bytes, ntiles, ws, ws_bytes, stream,
-                          abn);
-}
-
-static int fwd_bnstats_impl(const adaptseg_conv_desc *d, const float *x, const uint16_t *x_bf16,
-                            const float *const *w, const void *w_pack, float *y, uint16_t *y_bf16, float *stats,
-                            size_t stats_bytes, int *ntiles, void *ws, size_t ws_bytes, adaptseg_stream_t stream,
-                            const adaptseg_operand_bn *abn) {
-  AS_CHECK_ARG(ntiles && stats, "conv fwd_bnstats: null stats / ntiles");
-  *ntiles = 0;
-  Plan pl;
-  int st = make_plan(d, ADAPTSEG_CONV_FWD, pl);
-  if (st) return st;
-  AS_CHECK_ARG((x || x_bf16) && w && (y || y_bf16), "conv fwd_bnstats: null pointer");
-  AS_CHECK_ARG(y || !tapgemm_eligible(d), "conv fwd_bnstats: this product needs the fp32 output");
-  AS_CHECK_ARG(x || copy_only(pl, d, ADAPTSEG_CONV_FWD),
-               "conv fwd_bnstats: this product needs the fp32 input (no bf16-operand kernel for it)");
-  for (int s = 0; s < d->nseg; ++s) AS_CHECK_ARG(w[s], "conv fwd_bnstats: null weight %d", s);
-  AS_CHECK_ARG(!abn || !tapgemm_eligible(d), "conv fwd_bnstats_abn: no operand-BN kernel for this product");
-  if (tapgemm_eligible(d))  // the tap-GEMM path has no fused statistics: plain forward
-    return adaptseg_conv2d_fwd_x(d, x, x_bf16, w, nullptr, nullptr, nullptr, y, y_bf16, 0, ws, ws_bytes, stream);
-  ConvParams &p = pl.p;
-  p.x = x;
-  for (int s = 0; s < d->nseg; ++s) {
-    p.wt[s] = w[s];
-    if (reinterpret_cast<uintptr_t>(w[s]) & 15) pl.vb = pl.fast = false;
-  }
-  if (reinterpret_cast<uintptr_t>(x) & 15) pl.va = pl.fast = false;
-  set_splits(pl);
-  pl.act_ext = aligned16(x_bf16) ? x_bf16 : nullptr;
-  x3_terms(pl);
-  AS_CHECK_ARG(x || (copy_only(pl, d, ADAPTSEG_CONV_FWD) && pl.act_ext),
-               "conv fwd_bnstats: x is NULL but the plan (after the alignment checks) needs the fp32 input");
-  if (abn) {
-    AS_CHECK_ARG(abn_plan_ok(pl, d, ADAPTSEG_CONV_FWD),
-                 "conv fwd_bnstats_abn: no operand-BN kernel for this product (adaptseg_conv2d_operand_bn_ok)");
-    set_abn(p, abn);
-  }
-  const bool terms = copies_are_terms();
-  AS_CHECK_ARG(y || !terms, "conv fwd_bnstats: under the F32X3 maths the output is fp32");
-  const int64_t nyb = (int64_t)d->n * d->oh * d->ow * d->k;
-  const bool fused = terms && terms_in_epilogue(pl, y_bf16, nyb);
-  p.out = y;
-  p.outb = (terms && !fused) ? nullptr : reinterpret_cast<__bf16 *>(y_bf16);
-  p.outb_terms = fused ? 1 : 0;
-  p.flags = 0;
-  if (pl.fast && p.splits == 1) {
-    const int nt = (int)ceil_div(p.M, plan_bm(pl));
-    if ((size_t)(nt + 2 * (int64_t)p.N * nt) * sizeof(float) <= stats_bytes) {
-      p.stats = stats;
-      p.stats_ntiles = nt;
-      *ntiles = nt;
-    }
-  }
-  st = attach_wpack(pl, w_pack);
-  if (st) return st;
-  st = run_plan(pl, MODE_FWD, ws, ws_bytes, as_stream(stream));
-  return (st || !terms || fused) ? st : out_copy(y, y_bf16, nyb, d->k, as_stream(stream));
+  const FwdStats bn{stats, stats_bytes, ntiles, abn};
+  return fwd_impl(d, x_pre, nullptr, w, w_pack, nullptr, nullptr, y, nullptr, 0, ws, ws_bytes, stream, &bn);
 }
 
 int adaptseg_conv2d_bwd_data(const adaptseg_conv_desc *d, const float *dy, const float *const *w,
@@ -1360,8 +1375,9 @@ namespace adaptseg {
 // thin / tap-GEMM / per-element / split-K / stride-2 product)
 static int bnsum_plan_tiles(const Plan &pl, const adaptseg_conv_desc *d) {
   if (use_thin(d, ADAPTSEG_CONV_BWD_DATA) || tapgemm_eligible(d)) return 0;
-  if (!pl.fast || pl.s2 || pl.p.splits != 1 || pl.g16) return 0;   // (g16: compiled out, igemm_epilogue)
-  return (int)ceil_div(pl.p.M, plan_bm(pl));
+  if (pl.family == Family::Generic || pl.family == Family::Bf16Dma || pl.s2 || pl.p.splits != 1)
+    return 0;   // (Bf16Dma: compiled out, igemm_epilogue)
+  return (int)ceil_div(pl.p.M, pl.tile.bm);
 }
 
 // adaptseg_conv2d_bwd_data_xg, and with bs the fused BN backward sums where the final plan can
@@ -1401,16 +1417,9 @@ static int bwd_data_impl(const adaptseg_conv_desc *d, const float *dy, const uin
   }
   ConvParams &p = pl.p;
   p.dy = dy;
-  for (int s = 0; s < d->nseg; ++s) {
-    AS_CHECK_ARG(w[s], "conv bwd_data: null weight %d", s);
-    p.wt[s] = w[s];
-    if (reinterpret_cast<uintptr_t>(w[s]) & 15) pl.vb = pl.fast = false;
-  }
-  if (reinterpret_cast<uintptr_t>(dy) & 15) pl.va = pl.fast = false;
-  set_splits(pl);
-  pl.act_ext = aligned16(dy_bf16) ? dy_bf16 : nullptr;
-  x3_terms(pl);
-  AS_CHECK_ARG(dy || ((pl.g16 || pl.x3ext) && pl.act_ext),
+  for (int s = 0; s < d->nseg; ++s) p.wt[s] = w[s];
+  finish_plan(pl, aligned16(dy), segs_aligned(w, d->nseg), dy_bf16);
+  AS_CHECK_ARG(dy || ((pl.family == Family::Bf16Dma || pl.act_caller) && pl.act_ext),
                "conv bwd_data: dy is NULL but the plan (after the alignment checks) needs the fp32 dY");
   const bool terms = copies_are_terms();
   const bool fused = terms && terms_in_epilogue(pl, dx_bf16, nx);
@@ -1464,12 +1473,8 @@ int adaptseg_conv2d_bnsum_tiles(const adaptseg_conv_desc *d, int with_copy, int 
   AS_CHECK_ARG(ntiles, "conv2d_bnsum_tiles: null");
   *ntiles = 0;
   Plan pl;
-  int st = make_plan(d, ADAPTSEG_CONV_BWD_DATA, pl);
+  int st = query_plan(d, ADAPTSEG_CONV_BWD_DATA, Operands{true, true, with_copy != 0}, pl);
   if (st) return st;
-  if (with_copy) {
-    pl.act_ext = d;   // any non-NULL: the plan with the caller's copy of dY
-    x3_terms(pl);
-  }
   *ntiles = bnsum_plan_tiles(pl, d);
   return ADAPTSEG_OK;
 }
@@ -1542,15 +1547,8 @@ static int bwd_weight_impl(const adaptseg_conv_desc *d, const float *dy, const u
     p.dy = dy;
     p.x = x;
     for (int g = 0; g < d->nseg; ++g) p.dw[g] = dw[g];
-    if (reinterpret_cast<uintptr_t>(dy) & 15) pl.va = pl.fast = false;
-    if (reinterpret_cast<uintptr_t>(x) & 15) pl.vb = pl.fast = false;
-    set_splits(pl);
-    if (aligned16(dy_bf16) && aligned16(x_bf16) && dy_bf16 && x_bf16) {  // both copies or none
-      pl.act_ext = dy_bf16;
-      pl.act_ext2 = x_bf16;
-    }
-    x3_terms(pl);
-    AS_CHECK_ARG((dy && x) || ((pl.g16 || pl.x3ext) && pl.act_ext),
+    finish_plan(pl, aligned16(dy), aligned16(x), dy_bf16, x_bf16);
+    AS_CHECK_ARG((dy && x) || ((pl.family == Family::Bf16Dma || pl.act_caller) && pl.act_ext),
                  "conv bwd_weight: dy / x is NULL but the plan (after the alignment checks) needs the fp32 operands");
     if (abn) {
       AS_CHECK_ARG(abn_plan_ok(pl, d, ADAPTSEG_CONV_BWD_WEIGHT),

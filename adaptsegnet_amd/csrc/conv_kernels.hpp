@@ -1703,32 +1703,50 @@ __global__ void __launch_bounds__(64 * WAVES_M * WAVES_N, MINB) igemm_fast_kerne
 }
 
 
+// The kernel family a plan runs on.  make_plan chooses it (and the tile) once; finish_plan may
+// move the plan to Generic (a misaligned operand) or to X3Terms (the caller's term images); the
+// launchers, kernel_id and the workspace arithmetic only read it.  The weight-gradient kernel of
+// a family is the family with pl.mode == MODE_WGRAD.
+enum class Family {
+  Generic,   // per-element gather, fp32 MFMA (igemm_kernel): any operand
+  Fast,      // fp32 MFMA on vector / per-element FAST operands (igemm_fast_kernel)
+  Bf16,      // register-staged bf16 MFMA, packed bf16 weights (conv_bf16.hpp)
+  Bf16Dma,   // bf16 LDS-DMA on a bf16 activation copy (conv_bf16g.hpp), and its weight-gradient kernel
+  X3,        // F32X3 register-staged: exact 3-term bf16 splits made while staging (conv_x3.hpp)
+  X3Terms,   // F32X3 on pre-split term images by LDS-DMA (conv_x3r.hpp), and its weight-gradient kernel
+  X3Rows,    // F32X3 on the term-image tile, fp32 rows split in-kernel (igemm_x3h_kernel / igemm_x3hw_kernel)
+};
+inline bool is_x3(Family f) { return f == Family::X3 || f == Family::X3Terms || f == Family::X3Rows; }
+inline bool is_bf16(Family f) { return f == Family::Bf16 || f == Family::Bf16Dma; }
+
+struct Tile {
+  int bm, bn, bk, threads;
+};
+
 struct Plan {
   ConvParams p;
-  int cfg;        // index into kCfgBM / kCfgBN
-  bool va, vb;
-  bool fast;
-  bool s2;     // stride-2 data gradient by output-pixel parity class (grid.z = 4)
-  bool bf16;   // bf16-MFMA path (conv_bf16.hpp): 128x{128,256}x64 tiles, packed bf16 weights
-  bool x3;     // F32X3 path (conv_x3.hpp): fp32 via exact 3-term bf16 splits, 128x128x16 tiles
-  bool x3g;    // ... on pre-split term images by LDS-DMA (the caller's or made per call); with x3r
-  bool x3r;    // ... the 256x128x32 one-block-per-CU term-image kernel (conv_x3r.hpp)
-  int x3r_bm;  // its row tile (256; weight gradients with Cout < 256: 128)
-  bool x3r_ok; // F32X3 product the x3r kernel covers (a 32-deep step inside one tap, 16-B chunks)
-  bool x3ext;  // x3r on the caller's term images (F32X3 maths): no per-call split copies
-  bool x3h;    // ... x3r's 256x128x32 tile with the fp32 activation split in-kernel (igemm_x3h_kernel)
-  int bf16_bn; // its tile width: 256 for forward / data-grad products with N >= 256, else 128
-  bool g16;    // bf16 LDS-DMA kernel (conv_bf16g.hpp): bf16 activation copy, g16_bm x g16_bn x 64
-  int g16_bm, g16_bn, g16_bk;
-  const void *act_ext;  // caller's bf16 copy of the activation operand (g16; NULL: copied per call)
-  const void *act_ext2; // weight gradient: the caller's bf16 copy of x (act_ext: of dY)
+  Family family;
+  Tile tile;      // the family's block tile for this product (set where the family is chosen)
+  int cfg;        // Generic / Fast: index into kCfgBM / kCfgBN (selects the template instance)
+  bool va, vb;    // Generic: vector gathers of the A / B operand
+  bool s2;        // stride-2 data gradient by output-pixel parity class (grid.z = 4)
+  bool ae, be;    // Fast: per-element gathers for the A / B operand
+  bool terms_ok;  // F32X3 product the term-image tile covers (a 32-deep step inside one tap, 16-B chunks)
+  bool act_caller;  // X3Terms: the activation term images are the caller's (else made per call in ws)
+  const void *act_ext;  // caller's copy of the activation operand (Bf16Dma, X3Terms; NULL: copied per call)
+  const void *act_ext2; // weight gradient: the caller's copy of x (act_ext: of dY)
   const void *wpack_ext;  // caller-built weight pack (adaptseg_conv2d_wpack; NULL: packed per call)
-  bool ae, be; // FAST per-element gathers for the A / B operand
-  int bk;
   int mode;
   int tiles;
-  size_t slab_bytes;  // workspace need: [bf16 weight pack, 256-B aligned] + split-K slabs
+  size_t slab_bytes;  // workspace need: [weight pack + operand copies, 256-B aligned] + split-K slabs
   double flops;  // algorithmic FLOPs of the conv product this plan computes
+};
+
+// What a caller knows about one product's operands when its plan is finished (finish_plan): the
+// launch paths fill it from their pointers, the host queries state it.
+struct Operands {
+  bool a_aligned = true, b_aligned = true;   // the fp32 A / B operand is 16-B aligned
+  bool copies = false;   // the caller supplies the activation copies (weight gradient: both)
 };
 
 // tile configs: 0 = 128x128 (2x2 waves), 1 = 256x32 (4x1), 2 = 32x256 (1x4), 3 = 64x256 (1x4),
@@ -1745,8 +1763,12 @@ static int fast_bk(int cfg) { return (cfg == 4 || cfg == 6 || cfg == 8) ? 16 : 3
 
 // Planning and execution (conv_igemm.hip), shared with the tap-GEMM path (conv_tapgemm.hip).
 double conv_flops(const adaptseg_conv_desc *d);
-void set_splits(Plan &pl);
+// The plan's three phases: make_plan chooses family and tile for aligned operands, finish_plan
+// applies what the caller knows about the operands, set_splits (called by finish_plan) computes
+// tiles, splits and workspace bytes.  A plan is complete only after finish_plan.
 int make_plan(const adaptseg_conv_desc *d, int op, Plan &pl);
+void finish_plan(Plan &pl, const Operands &ops);
+void set_splits(Plan &pl);
 int kernel_id(const Plan &pl, int mode);
 // defer: a weight gradient whose plan splits K leaves its sum pending on stream s
 // (adaptseg_splitk_flush) instead of launching it
@@ -1776,7 +1798,6 @@ hipError_t prep_bf16_wpack(const Plan &pl, void *pack, hipStream_t s);   // the 
 hipError_t launch_bf16(const Plan &pl, void *ws, hipStream_t s);
 // F32X3 conv math: three-image weight-pack bytes and launcher (conv_launch_x3.hip)
 size_t x3_wpack_bytes(const Plan &pl);
-int plan_bm(const Plan &pl);
 size_t x3_pre_bytes(const Plan &pl);   // workspace ahead of the slabs: weight pack + per-call term images
 hipError_t prep_x3(const Plan &pl, void *wpack, hipStream_t s);    // the weight pack (unless wpack_ext) + copies
 hipError_t prep_x3_wpack(const Plan &pl, void *pack, hipStream_t s);  // the weight pack alone

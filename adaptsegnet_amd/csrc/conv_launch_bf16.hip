@@ -103,12 +103,12 @@ __global__ void bf16_copy_kernel(const float *__restrict__ x, int n, int h, int 
 // (weight gradient: dY's copy, then x's)
 static size_t g16_act_elems(const Plan &pl) {
   const ConvParams &p = pl.p;
-  if (!pl.g16) return 0;
+  if (pl.family != Family::Bf16Dma) return 0;
   return pl.mode == MODE_FWD ? (size_t)p.n * p.h * p.w * p.c : (size_t)p.n * p.oh * p.ow * p.k;
 }
 static size_t g16_act2_elems(const Plan &pl) {
   const ConvParams &p = pl.p;
-  return pl.g16 && pl.mode == MODE_WGRAD ? (size_t)p.n * p.h * p.w * p.c : 0;
+  return pl.family == Family::Bf16Dma && pl.mode == MODE_WGRAD ? (size_t)p.n * p.h * p.w * p.c : 0;
 }
 static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
@@ -154,7 +154,7 @@ hipError_t prep_bf16(Plan &pl, void *wpack, hipStream_t s) {
     if (e != hipSuccess) return e;
   }
   // the activation operands' bf16 copies the caller did not supply, after the (256-B aligned) weight pack
-  if (pl.g16) {
+  if (pl.family == Family::Bf16Dma) {
     char *base = reinterpret_cast<char *>(wpack) + al256(bf16_wpack_bytes(pl));
     uint4 *act = reinterpret_cast<uint4 *>(base);
     const int64_t n8 = (int64_t)g16_act_elems(pl) / 8;
@@ -179,61 +179,56 @@ hipError_t prep_bf16(Plan &pl, void *wpack, hipStream_t s) {
 hipError_t launch_bf16(const Plan &pl, void *wpack, hipStream_t s) {
   const ConvParams &p = pl.p;
   const __bf16 *wb = reinterpret_cast<const __bf16 *>(pl.wpack_ext ? pl.wpack_ext : wpack);
-  if (pl.g16) {
+  const Tile &t = pl.tile;
+  const bool bn256 = t.bn == 256;
+  dim3 grid(pl.tiles, p.splits, pl.s2 ? 4 : 1), block(t.threads);
+  if (pl.family == Family::Bf16Dma) {
     const char *base = reinterpret_cast<const char *>(wpack) + al256(bf16_wpack_bytes(pl));
-    const __bf16 *act = pl.act_ext ? reinterpret_cast<const __bf16 *>(pl.act_ext)
-                                   : reinterpret_cast<const __bf16 *>(base);
-    dim3 grid(pl.tiles, p.splits, pl.s2 ? 4 : 1), block(512);
+    const __bf16 *act = reinterpret_cast<const __bf16 *>(pl.act_ext ? pl.act_ext : base);
     if (pl.s2) {   // stride-2 data gradient: parity classes on grid.z, K step 32
-      if (pl.g16_bn == 256) launch_k(igemm_bf16g_kernel<MODE_DGRAD, 128, 256, 32, true>, grid, block, s, p, act, wb);
+      if (bn256) launch_k(igemm_bf16g_kernel<MODE_DGRAD, 128, 256, 32, true>, grid, block, s, p, act, wb);
       else launch_k(igemm_bf16g_kernel<MODE_DGRAD, 256, 128, 32, true>, grid, block, s, p, act, wb);
-      return hipGetLastError();
-    }
-    if (pl.mode == MODE_WGRAD) {
-      const __bf16 *act2 = pl.act_ext2 ? reinterpret_cast<const __bf16 *>(pl.act_ext2)
-                                       : reinterpret_cast<const __bf16 *>(
-                                             base + al256(g16_act_elems(pl) * sizeof(__bf16)));
+    } else if (pl.mode == MODE_WGRAD) {
+      const __bf16 *act2 = reinterpret_cast<const __bf16 *>(
+          pl.act_ext2 ? pl.act_ext2 : base + al256(g16_act_elems(pl) * sizeof(__bf16)));
       // (a 6-deep ring for the 256x128 tile, 4-deep for 128x128 — five / three steps in flight
       // instead of two: per shape within +-3 %, c5 -0.6 %, profiles/r5/g16_wgrad_ring_ab.txt)
-      if (pl.g16_bn == 256) launch_k(igemm_bf16g_wgrad_kernel<256, 256, 2>, grid, dim3(1024), s, p, act, act2);
-      else if (pl.g16_bm == 256) launch_k(igemm_bf16g_wgrad_kernel<256>, grid, block, s, p, act, act2);
+      if (bn256) launch_k(igemm_bf16g_wgrad_kernel<256, 256, 2>, grid, block, s, p, act, act2);
+      else if (t.bm == 256) launch_k(igemm_bf16g_wgrad_kernel<256>, grid, block, s, p, act, act2);
       else launch_k(igemm_bf16g_wgrad_kernel<128>, grid, block, s, p, act, act2);
-      return hipGetLastError();
-    }
-#define G16_LAUNCH(MODE_, BK_)                                                                  \
-  do {                                                                                          \
-    if (pl.g16_bm == 256 && pl.g16_bn == 256)                                                   \
-      launch_k(igemm_bf16g_kernel<MODE_, 256, 256, 64, false, 2>, grid, dim3(1024), s, p, act, wb); \
-    else if (pl.g16_bn == 256) launch_k(igemm_bf16g_kernel<MODE_, 128, 256, BK_>, grid, block, s, p, act, wb); \
-    else launch_k(igemm_bf16g_kernel<MODE_, 256, 128, BK_>, grid, block, s, p, act, wb);          \
-  } while (0)
-    if (pl.mode == MODE_FWD) {
-      if (pl.g16_bk == 64) G16_LAUNCH(MODE_FWD, 64);
-      else G16_LAUNCH(MODE_FWD, 32);
     } else {
-      if (pl.g16_bk == 64) G16_LAUNCH(MODE_DGRAD, 64);
+#define G16_LAUNCH(MODE_, BK_)                                                                     \
+  do {                                                                                             \
+    if (t.bm == 256 && bn256)                                                                      \
+      launch_k(igemm_bf16g_kernel<MODE_, 256, 256, 64, false, 2>, grid, block, s, p, act, wb);     \
+    else if (bn256) launch_k(igemm_bf16g_kernel<MODE_, 128, 256, BK_>, grid, block, s, p, act, wb); \
+    else launch_k(igemm_bf16g_kernel<MODE_, 256, 128, BK_>, grid, block, s, p, act, wb);           \
+  } while (0)
+      if (pl.mode == MODE_FWD && t.bk == 64) G16_LAUNCH(MODE_FWD, 64);
+      else if (pl.mode == MODE_FWD) G16_LAUNCH(MODE_FWD, 32);
+      else if (t.bk == 64) G16_LAUNCH(MODE_DGRAD, 64);
       else G16_LAUNCH(MODE_DGRAD, 32);
-    }
 #undef G16_LAUNCH
+    }
     return hipGetLastError();
   }
-  const bool w256 = pl.bf16_bn == 256 && pl.mode != MODE_WGRAD;
-  dim3 grid(pl.tiles, p.splits, pl.s2 ? 4 : 1), block(bf16_threads(pl.mode));
-  if (pl.mode == MODE_FWD && pl.act_ext) {   // the caller's bf16 activation copy (bf16 activation storage)
-    const __bf16 *act = reinterpret_cast<const __bf16 *>(pl.act_ext);
-    if (w256) launch_k(igemm_bf16_kernel<MODE_FWD, false, 256, true>, grid, block, s, p, wb, act);
+  // Family::Bf16, the register-staged kernel; act: the caller's bf16 activation copy (forward
+  // under bf16 activation storage), else NULL
+  const __bf16 *act = pl.mode == MODE_FWD ? reinterpret_cast<const __bf16 *>(pl.act_ext) : nullptr;
+  if (pl.mode == MODE_FWD && act) {
+    if (bn256) launch_k(igemm_bf16_kernel<MODE_FWD, false, 256, true>, grid, block, s, p, wb, act);
     else launch_k(igemm_bf16_kernel<MODE_FWD, false, 128, true>, grid, block, s, p, wb, act);
   } else if (pl.mode == MODE_FWD) {
-    if (w256) launch_k(igemm_bf16_kernel<MODE_FWD, false, 256>, grid, block, s, p, wb, (const __bf16 *)nullptr);
-    else launch_k(igemm_bf16_kernel<MODE_FWD, false, 128>, grid, block, s, p, wb, (const __bf16 *)nullptr);
+    if (bn256) launch_k(igemm_bf16_kernel<MODE_FWD, false, 256>, grid, block, s, p, wb, act);
+    else launch_k(igemm_bf16_kernel<MODE_FWD, false, 128>, grid, block, s, p, wb, act);
   } else if (pl.mode == MODE_DGRAD && pl.s2) {
-    if (w256) launch_k(igemm_bf16_kernel<MODE_DGRAD, true, 256>, grid, block, s, p, wb, (const __bf16 *)nullptr);
-    else launch_k(igemm_bf16_kernel<MODE_DGRAD, true, 128>, grid, block, s, p, wb, (const __bf16 *)nullptr);
+    if (bn256) launch_k(igemm_bf16_kernel<MODE_DGRAD, true, 256>, grid, block, s, p, wb, act);
+    else launch_k(igemm_bf16_kernel<MODE_DGRAD, true, 128>, grid, block, s, p, wb, act);
   } else if (pl.mode == MODE_DGRAD) {
-    if (w256) launch_k(igemm_bf16_kernel<MODE_DGRAD, false, 256>, grid, block, s, p, wb, (const __bf16 *)nullptr);
-    else launch_k(igemm_bf16_kernel<MODE_DGRAD, false, 128>, grid, block, s, p, wb, (const __bf16 *)nullptr);
+    if (bn256) launch_k(igemm_bf16_kernel<MODE_DGRAD, false, 256>, grid, block, s, p, wb, act);
+    else launch_k(igemm_bf16_kernel<MODE_DGRAD, false, 128>, grid, block, s, p, wb, act);
   } else {
-    launch_k(igemm_bf16_kernel<MODE_WGRAD, false, 128>, grid, block, s, p, wb, (const __bf16 *)nullptr);
+    launch_k(igemm_bf16_kernel<MODE_WGRAD, false, 128>, grid, block, s, p, wb, act);
   }
   return hipGetLastError();
 }

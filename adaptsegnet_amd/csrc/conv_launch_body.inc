@@ -8,7 +8,7 @@ namespace adaptseg {
 
 #define AS_LAUNCH(BM_, BN_, WM_, WN_, FBK_)                                                  \
   do {                                                                                       \
-    if (pl.fast) {                                                                           \
+    if (pl.family == Family::Fast) {                                                         \
       const int v = (pl.s2 ? 4 : 0) | (pl.ae ? 2 : 0) | (pl.be ? 1 : 0);                     \
       switch (v) {                                                                           \
         case 0: AS_FAST(BM_, BN_, WM_, WN_, FBK_, false, false, false); break;              \
@@ -33,13 +33,13 @@ namespace adaptseg {
 template <int MODE>
 static hipError_t launch_cfg(const Plan &pl, hipStream_t s) {
   constexpr int MINB_ = 1;
-  dim3 grid(pl.tiles, pl.p.splits, pl.s2 ? 4 : 1), block(kCfgThreads[pl.cfg]);
+  dim3 grid(pl.tiles, pl.p.splits, pl.s2 ? 4 : 1), block(pl.tile.threads);
   switch (pl.cfg) {
     case 0:
       // stride-1 vector data gradients (the 3x3 ones): the min-blocks-2 build (157 VGPRs, the
       // accumulators out of AGPRs, no SGPR spills; +0.3 % c2, +-0 c3 over min-blocks 1)
       if constexpr (MODE == MODE_DGRAD) {
-        if (pl.fast && !pl.s2 && !pl.ae && !pl.be) {
+        if (pl.family == Family::Fast && !pl.s2 && !pl.ae && !pl.be) {
           launch_k(igemm_fast_kernel<MODE, 128, 128, 2, 2, 32, false, false, false, 2>, grid, block, s, pl.p);
           break;
         }
@@ -57,7 +57,7 @@ static hipError_t launch_cfg(const Plan &pl, hipStream_t s) {
     case 7: AS_LAUNCH(256, 128, 4, 2, 32); break;
     default:
       // cfg 8: occupancy-3 build of the BK-16 tile (vector FAST operands only)
-      if (!pl.fast || pl.s2 || pl.ae || pl.be) return hipErrorInvalidValue;
+      if (pl.family != Family::Fast || pl.s2 || pl.ae || pl.be) return hipErrorInvalidValue;
       launch_k(igemm_fast_kernel<MODE, 128, 128, 2, 2, 16, false, false, false, 3>, grid, block, s, pl.p);
       break;
   }

@@ -26,23 +26,23 @@ size_t x3_wpack_bytes(const Plan &pl) {
 // elements of the x3r kernel's activation operand (FWD: x, DGRAD / WGRAD: dY) and, for the
 // weight gradient, of x: their term images (made per call when the caller supplies none) are
 // three times that many bf16
-size_t x3g_act_elems(const Plan &pl) {
+static size_t x3_act_elems(const Plan &pl) {
   const ConvParams &p = pl.p;
-  if (!pl.x3g) return 0;   // (x3ext: the caller's images have this size too, see launch_x3)
+  if (pl.family != Family::X3Terms) return 0;   // (the caller's images have this size too, see launch_x3)
   return pl.mode == MODE_FWD ? (size_t)p.n * p.h * p.w * p.c : (size_t)p.n * p.oh * p.ow * p.k;
 }
-size_t x3g_act2_elems(const Plan &pl) {
+static size_t x3_act2_elems(const Plan &pl) {
   const ConvParams &p = pl.p;
-  return pl.x3g && pl.mode == MODE_WGRAD ? (size_t)p.n * p.h * p.w * p.c : 0;
+  return pl.family == Family::X3Terms && pl.mode == MODE_WGRAD ? (size_t)p.n * p.h * p.w * p.c : 0;
 }
 static size_t al256(size_t b) { return (b + 255) / 256 * 256; }
 
 // workspace ahead of the split-K slabs: [weight pack][three term images of the activation
 // operand (+ of x for the weight gradient) when the caller supplied none]
 size_t x3_pre_bytes(const Plan &pl) {
-  if (pl.x3ext && pl.x3r) return al256(x3_wpack_bytes(pl));   // the caller's term images
-  return al256(x3_wpack_bytes(pl)) + al256(3 * x3g_act_elems(pl) * sizeof(__bf16)) +
-         al256(3 * x3g_act2_elems(pl) * sizeof(__bf16));
+  if (pl.act_caller) return al256(x3_wpack_bytes(pl));   // the caller's term images
+  return al256(x3_wpack_bytes(pl)) + al256(3 * x3_act_elems(pl) * sizeof(__bf16)) +
+         al256(3 * x3_act2_elems(pl) * sizeof(__bf16));
 }
 
 static void split_copy(const float *x, int n, int h, int w, int c, int sxn, int sxh, int sxw, void *out,
@@ -69,14 +69,14 @@ hipError_t prep_x3(const Plan &pl, void *wpack, hipStream_t s) {
     const hipError_t e = prep_x3_wpack(pl, wpack, s);
     if (e != hipSuccess) return e;
   }
-  if (pl.x3g) {   // the operands' term images the caller did not supply
+  if (pl.family == Family::X3Terms) {   // the operands' term images the caller did not supply
     char *base = reinterpret_cast<char *>(wpack) + al256(x3_wpack_bytes(pl));
     if (!pl.act_ext) {
       if (pl.mode == MODE_FWD) split_copy(p.x, p.n, p.h, p.w, p.c, p.sxn, p.sxh, p.sxw, base, s);
       else split_copy(p.dy, p.n, p.oh, p.ow, p.k, p.oh * p.ow * p.k, p.ow * p.k, p.k, base, s);
     }
     if (pl.mode == MODE_WGRAD && !pl.act_ext2)
-      split_copy(p.x, p.n, p.h, p.w, p.c, p.sxn, p.sxh, p.sxw, base + al256(3 * x3g_act_elems(pl) * sizeof(__bf16)),
+      split_copy(p.x, p.n, p.h, p.w, p.c, p.sxn, p.sxh, p.sxw, base + al256(3 * x3_act_elems(pl) * sizeof(__bf16)),
                  s);
   }
   return hipGetLastError();
@@ -85,36 +85,39 @@ hipError_t prep_x3(const Plan &pl, void *wpack, hipStream_t s) {
 hipError_t launch_x3(const Plan &pl, void *wpack, hipStream_t s) {
   const ConvParams &p = pl.p;
   const __bf16 *wb = reinterpret_cast<const __bf16 *>(pl.wpack_ext ? pl.wpack_ext : wpack);
-  dim3 grid(pl.tiles, p.splits, pl.s2 ? 4 : 1), block(x3_threads(pl.mode));
-  if (pl.x3r) {
-    const char *base = reinterpret_cast<const char *>(wpack) + al256(x3_wpack_bytes(pl));
-    const __bf16 *act = pl.act_ext ? reinterpret_cast<const __bf16 *>(pl.act_ext) : reinterpret_cast<const __bf16 *>(base);
-    if (pl.mode == MODE_FWD) launch_k(igemm_x3r_kernel<MODE_FWD, false>, grid, 512, s, p, act, wb);
-    else if (pl.mode == MODE_DGRAD && pl.s2) launch_k(igemm_x3r_kernel<MODE_DGRAD, true>, grid, 512, s, p, act, wb);
-    else if (pl.mode == MODE_DGRAD) launch_k(igemm_x3r_kernel<MODE_DGRAD, false>, grid, 512, s, p, act, wb);
-    else {
-      const __bf16 *act2 = pl.act_ext2 ? reinterpret_cast<const __bf16 *>(pl.act_ext2)
-                                       : reinterpret_cast<const __bf16 *>(base + al256(3 * x3g_act_elems(pl) * sizeof(__bf16)));
-      if (pl.x3r_bm == 256) launch_k(igemm_x3r_wgrad_kernel<256>, grid, 512, s, p, act, act2);
-      else launch_k(igemm_x3r_wgrad_kernel<128>, grid, 512, s, p, act, act2);
+  const int mode = pl.mode;
+  dim3 grid(pl.tiles, p.splits, pl.s2 ? 4 : 1), block(pl.tile.threads);
+  switch (pl.family) {
+    case Family::X3Terms: {
+      const char *base = reinterpret_cast<const char *>(wpack) + al256(x3_wpack_bytes(pl));
+      const __bf16 *act = reinterpret_cast<const __bf16 *>(pl.act_ext ? pl.act_ext : base);
+      if (mode == MODE_FWD) launch_k(igemm_x3r_kernel<MODE_FWD, false>, grid, block, s, p, act, wb);
+      else if (mode == MODE_DGRAD && pl.s2) launch_k(igemm_x3r_kernel<MODE_DGRAD, true>, grid, block, s, p, act, wb);
+      else if (mode == MODE_DGRAD) launch_k(igemm_x3r_kernel<MODE_DGRAD, false>, grid, block, s, p, act, wb);
+      else {
+        const __bf16 *act2 = reinterpret_cast<const __bf16 *>(
+            pl.act_ext2 ? pl.act_ext2 : base + al256(3 * x3_act_elems(pl) * sizeof(__bf16)));
+        if (pl.tile.bm == 256) launch_k(igemm_x3r_wgrad_kernel<256>, grid, block, s, p, act, act2);
+        else launch_k(igemm_x3r_wgrad_kernel<128>, grid, block, s, p, act, act2);
+      }
+      break;
     }
-    return hipGetLastError();
+    case Family::X3Rows:
+      if (mode == MODE_WGRAD) launch_k(igemm_x3hw_kernel<128>, grid, block, s, p);   // (the only row tile: choose_x3)
+      else if (mode == MODE_FWD && p.abn_m) launch_k(igemm_x3h_abn_kernel, grid, block, s, p, wb);
+      else if (mode == MODE_FWD) launch_k(igemm_x3h_kernel<MODE_FWD, false>, grid, block, s, p, wb);
+      else if (pl.s2) launch_k(igemm_x3h_kernel<MODE_DGRAD, true>, grid, block, s, p, wb);
+      else launch_k(igemm_x3h_kernel<MODE_DGRAD, false>, grid, block, s, p, wb);
+      break;
+    case Family::X3:
+      if (mode == MODE_FWD) launch_k(igemm_x3_kernel<MODE_FWD, false>, grid, block, s, p, wb);
+      else if (mode == MODE_DGRAD && pl.s2) launch_k(igemm_x3_kernel<MODE_DGRAD, true>, grid, block, s, p, wb);
+      else if (mode == MODE_DGRAD) launch_k(igemm_x3_kernel<MODE_DGRAD, false>, grid, block, s, p, wb);
+      else if (p.abn_m) launch_k(igemm_x3_abn_kernel, grid, block, s, p, wb);
+      else launch_k(igemm_x3_kernel<MODE_WGRAD, false>, grid, block, s, p, wb);
+      break;
+    default: return hipErrorInvalidValue;
   }
-  if (pl.x3h) {
-    // (the 256-row weight-gradient tile needs two register sets of six float4 beside its 128
-    // accumulators: it spills, so the weight gradient runs the 128-row tile)
-    if (pl.mode == MODE_WGRAD) launch_k(igemm_x3hw_kernel<128>, grid, 512, s, p);
-    else if (pl.mode == MODE_FWD && p.abn_m) launch_k(igemm_x3h_abn_kernel, grid, 512, s, p, wb);
-    else if (pl.mode == MODE_FWD) launch_k(igemm_x3h_kernel<MODE_FWD, false>, grid, 512, s, p, wb);
-    else if (pl.s2) launch_k(igemm_x3h_kernel<MODE_DGRAD, true>, grid, 512, s, p, wb);
-    else launch_k(igemm_x3h_kernel<MODE_DGRAD, false>, grid, 512, s, p, wb);
-    return hipGetLastError();
-  }
-  if (pl.mode == MODE_FWD) launch_k(igemm_x3_kernel<MODE_FWD, false>, grid, block, s, p, wb);
-  else if (pl.mode == MODE_DGRAD && pl.s2) launch_k(igemm_x3_kernel<MODE_DGRAD, true>, grid, block, s, p, wb);
-  else if (pl.mode == MODE_DGRAD) launch_k(igemm_x3_kernel<MODE_DGRAD, false>, grid, block, s, p, wb);
-  else if (p.abn_m) launch_k(igemm_x3_abn_kernel, grid, block, s, p, wb);
-  else launch_k(igemm_x3_kernel<MODE_WGRAD, false>, grid, block, s, p, wb);
   return hipGetLastError();
 }
 

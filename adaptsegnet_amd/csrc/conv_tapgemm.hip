@@ -166,7 +166,7 @@ static int inner_plan(const adaptseg_conv_desc *d, int op, Plan &pl) {
   adaptseg_conv_desc e = inner_desc(d);
   int st = make_plan(&e, op, pl);
   if (st) return st;
-  set_splits(pl);
+  finish_plan(pl, Operands{});
   pl.flops = conv_flops(d);
   return ADAPTSEG_OK;
 }
@@ -193,7 +193,7 @@ int tapgemm_kernel_id(const adaptseg_conv_desc *d, int op, int *kid, int *splits
 bool tapgemm_copy_only(const adaptseg_conv_desc *d, int op) {
   Plan pl;
   if (op == ADAPTSEG_CONV_BWD_DATA || inner_plan(d, op, pl)) return false;
-  return pl.g16;
+  return pl.family == Family::Bf16Dma;
 }
 
 static int need_ws(const adaptseg_conv_desc *d, int op, size_t ws_bytes, void *ws) {
@@ -228,7 +228,8 @@ int tapgemm_fwd(const adaptseg_conv_desc *d, const float *x, const uint16_t *x_b
   // the operand copy: read by the bf16 LDS-DMA kernels (BF16 maths) and, under F32X3_PRESPLIT,
   // as the term images of x by the inner x3r kernel (which then skips its per-call split)
   pl.act_ext = (reinterpret_cast<uintptr_t>(x_bf16) & 15) ? nullptr : x_bf16;
-  AS_CHECK_ARG(x || (pl.g16 && pl.act_ext), "conv fwd (tap-GEMM): x is NULL and the inner GEMM needs it");
+  AS_CHECK_ARG(x || (pl.family == Family::Bf16Dma && pl.act_ext),
+               "conv fwd (tap-GEMM): x is NULL and the inner GEMM needs it");
   pl.p.wt[0] = wp;
   pl.p.out = z;
   pl.p.flags = 0;
@@ -290,7 +291,8 @@ int tapgemm_bwd_weight(const adaptseg_conv_desc *d, const float *dy, const float
   pl.p.dy = gbuf;
   pl.p.x = x;
   pl.act_ext2 = (reinterpret_cast<uintptr_t>(x_bf16) & 15) ? nullptr : x_bf16;   // x's copy; dY's is made here
-  AS_CHECK_ARG(x || (pl.g16 && pl.act_ext2), "conv bwd_weight (tap-GEMM): x is NULL and the inner GEMM needs it");
+  AS_CHECK_ARG(x || (pl.family == Family::Bf16Dma && pl.act_ext2),
+               "conv bwd_weight (tap-GEMM): x is NULL and the inner GEMM needs it");
   pl.p.dw[0] = dwp;
   pl.p.flags = 0;
   st = run_plan(pl, MODE_WGRAD, gws, gws_bytes, s);

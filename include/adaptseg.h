@@ -95,11 +95,12 @@ int adaptseg_conv_set_math(int math);
 int adaptseg_conv_get_math(int *math);
 /* Kernel-selection options, process-wide (set before sizing workspaces, like the maths); the
    initial values come from the environment variables named below.
-     ADAPTSEG_OPT_X3H (ADAPTSEG_X3H, default 0): F32X3 maths, bit 1 / 2 / 4 = forward / data-gradient
-       / weight-gradient products that the 256x128x32 term-image tiles cover (a 32-deep K step inside
-       one tap) run on igemm_x3h_kernel / igemm_x3hw_kernel<128> — those tiles with the fp32 operands
-       split in-kernel, no term images — instead of the register-staged 128x128x16 kernel.  Same
-       arithmetic (bitwise the term-image kernels' results on the same plan).
+     ADAPTSEG_OPT_X3H (ADAPTSEG_X3H, default 3, K >= 512): F32X3 maths, bit 1 / 2 / 4 = forward /
+       data-gradient / weight-gradient products that the 256x128x32 term-image tiles cover (a 32-deep
+       K step inside one tap) run on igemm_x3h_kernel / igemm_x3hw_kernel<128> — those tiles with the
+       fp32 operands split in-kernel, no term images — instead of the register-staged 128x128x16
+       kernel; forward / data gradient only at K >= 512 and not on the stride-2 parity classes.
+       Same arithmetic (bitwise the term-image kernels' results on the same plan).
      ADAPTSEG_OPT_G16_WIDE (ADAPTSEG_G16_WIDE, default 1): BF16 maths, bit 1 = forward /
        data-gradient products with N >= 256 and K >= 2048 on the 256x256x64 two-stage LDS-DMA
        tile, bit 2 = weight gradients with Cout >= 256 and N >= 256 on the 256x256 tile with
@@ -659,12 +660,36 @@ int adaptseg_add_i64(int64_t *p, int64_t n, int64_t v, adaptseg_stream_t stream)
 /* pair, which records the kernel's own execution (start to end, as rocprofv3 reports it,   */
 /* not the stream time it spent queued behind other streams' work); the summed durations    */
 /* and summed algorithmic FLOPs (2*N*OH*OW*K*C*KH*KW*nseg per launch) are read              */
-/* back after a device synchronise.  selector = -1: every igemm launch; otherwise           */
-/* selector = 100*op + 10*tile + variant names ONE kernel symbol: op 0 fwd, 1 bwd-data,     */
-/* 2 bwd-weight; tile 0 = 128x128, 1 = 256x32, 2 = 32x256, 3 = 64x256, 4 = 256x64;          */
-/* variant 0..3 = generic gather (2*vecA + vecB), 4 = FAST, 5 = FAST stride-2 parity path;    */
-/* tile 9 = the bf16-MFMA kernels: variant 0 / 1 bf16 operands (stride-2 parity path),      */
-/* 2 / 3 the same on the 128x256 tile, 5 / 6 the F32X3 kernel (3-term bf16 splits).          */
+/* back after a device synchronise.  selector = -1: every igemm launch; otherwise the        */
+/* selector names ONE kernel symbol.                                                         */
+/*                                                                                           */
+/* Kernel selectors: 100*op + id, op 0 fwd, 1 bwd-data, 2 bwd-weight (written from the       */
+/* selector table of conv_igemm.hip, kSelectors / kernel_id).  "s2" = the stride-2 data      */
+/* gradient by output-pixel parity class (op 1 only).  Tiles are rows x columns x K step.    */
+/*   fp32 MFMA, id = 10*cfg + variant                                                        */
+/*     cfg 0 = 128x128x32, 1 = 256x32, 2 = 32x256, 3 = 64x256, 4 = 256x64 (K step 16),       */
+/*         5 = 64x64, 6 = 128x128x16, 7 = 256x128 (8 waves), 8 = 128x128x16 built for        */
+/*         3 blocks per CU (2, 3, 5: weight gradients only; 8: vector stride-1 operands only)*/
+/*     variant 0..3  generic per-element gather: 2*(vector A) + (vector B)                   */
+/*     variant 4..9  FAST: 4 + 4*s2 + 2*(per-element A) + (per-element B)                    */
+/*   80  the thin kernels (Cout <= 4, conv_thin.hip)                                         */
+/*   bf16-MFMA families (they reuse ids of FAST cfg-8 variants that do not exist)            */
+/*     85  bf16 LDS-DMA 256x256x64, two stages (ADAPTSEG_OPT_G16_WIDE); op 2: its 256x256    */
+/*         weight-gradient tile with 64-pixel K steps                                        */
+/*     86  F32X3 on fp32 rows (x3h), 256x128x32; op 0 / 1                                    */
+/*     87  ... its s2 form (never planned); op 2: the 128-row x3hw weight gradient (the      */
+/*         256-row one would be 286: not built)                                              */
+/*     88  F32X3 on term images, 256x128x32; op 2: the 256-row weight gradient               */
+/*     89  ... its s2 form; op 2: the 128-row weight gradient                                */
+/*     90 / 91  register-staged bf16 128x128x64 / its s2 form                                */
+/*     92 / 93  register-staged bf16 128x256x64 (ADAPTSEG_MATH_BF16_WIDE) / its s2 form;     */
+/*         op 1: 192 / 193 are the bf16 LDS-DMA s2 forms, 128x256x32 / 256x128x32            */
+/*     94  bf16 LDS-DMA 128x256x32                                                           */
+/*     95 / 96  F32X3 register-staged 128x128x16 / its s2 form                               */
+/*     97  bf16 LDS-DMA 128x256x64                                                           */
+/*     98  bf16 LDS-DMA 256x128x64; op 2: the 256x128 weight gradient (32-pixel K steps)     */
+/*     99  bf16 LDS-DMA 256x128x32; op 2: the 128x128 weight gradient                        */
+/* A tap-GEMM product (ASPP) reports the selector of its inner 1x1 GEMM.                     */
 /* ------------------------------------------------------------------------------------ */
 int adaptseg_timing_enable(int enable, int selector);
 int adaptseg_timing_read(double *total_ms, double *total_flops, int64_t *launches);

@@ -142,6 +142,48 @@ def test_conv_fwd_dgrad_wgrad(case, conv_math):
     assert rel(dws[0].permute(0, 3, 1, 2).cpu(), 2 * wr[0].grad) < 2e-5
 
 
+@pytest.mark.parametrize("math", ["f32x3", "bf16"])
+@pytest.mark.parametrize("which", ["fwd_x", "fwd_w", "dgrad_dy", "wgrad_x"])
+def test_conv_misaligned_input_downgrades(which, math):
+    """An input operand one float off a 16-B boundary: the aligned plan of this product (K = 576,
+    M = 256: the x3h tile under F32X3, the LDS-DMA tile under BF16, split along K, with a weight
+    pack) is downgraded at launch to the generic fp32 gather kernel — another kernel, split count
+    and workspace layout at once.  The generic kernel is fp32 under every maths, so the fp32
+    bound holds for the BF16 cases too."""
+    from test_epilogue_paths_gpu import off_by_one
+    k = K()
+    n, c, h, w = 1, 64, 16, 16
+    geom = k.ConvGeom(c, c, 3, 3, 1, (1,), (1,))
+    g = torch.Generator().manual_seed(31)
+    x = torch.randn(n, c, h, w, generator=g, dtype=torch.float64)
+    wt = torch.randn(c, c, 3, 3, generator=g, dtype=torch.float64) * 0.1
+    xr, wr = x.clone().requires_grad_(True), wt.clone().requires_grad_(True)
+    ref = F.conv2d(xr, wr, None, 1, 1)
+    gy = torch.randn(ref.shape, generator=g, dtype=torch.float64)
+    ref.backward(gy)
+    k.set_conv_math({"f32x3": k.MATH_F32X3, "bf16": k.MATH_BF16}[math])
+    try:
+        op = {"fwd_x": 0, "fwd_w": 0, "dgrad_dy": 1, "wgrad_x": 2}[which]
+        kid, splits = k.conv_kernel_id(geom, n, h, w, op)
+        assert kid % 100 >= 85 and splits > 1, (kid, splits)   # the aligned plan: an MFMA-bf16 tile, split-K
+        with k.weight_pack_scope():   # the aligned weights' pack is built; the downgraded plan ignores it
+            if which == "fwd_x":
+                y = k.conv_fwd(geom, off_by_one(nhwc(x)), n, h, w, [w_cl(wt)])
+                assert rel(nchw(y), ref) < 2e-5
+            elif which == "fwd_w":
+                y = k.conv_fwd(geom, nhwc(x), n, h, w, [off_by_one(w_cl(wt))])
+                assert rel(nchw(y), ref) < 2e-5
+            elif which == "dgrad_dy":
+                dx = k.conv_dgrad(geom, off_by_one(nhwc(gy)), n, h, w, [w_cl(wt)])
+                assert rel(nchw(dx), xr.grad) < 2e-5
+            else:
+                dw = torch.zeros_like(w_cl(wt))
+                k.conv_wgrad(geom, nhwc(gy), off_by_one(nhwc(x)), n, h, w, [dw])
+                assert rel(dw.permute(0, 3, 1, 2).cpu(), wr.grad) < 2e-5
+    finally:
+        k.set_conv_math(k.MATH_F32X3)   # the library default
+
+
 def test_conv_epilogues():
     k = K()
     g = torch.Generator().manual_seed(5)

@@ -1,6 +1,7 @@
 """igemm_x3h_kernel (conv_x3r.hpp, selectors 100*op + 86 / 87): the 256x128x32 F32X3 tile with the
 fp32 activation operand split in-kernel, and igemm_x3hw_kernel<128> (selector 287), the 128-row
-weight-gradient tile with both fp32 operands split in-kernel (adaptseg_conv_set_x3h / ADAPTSEG_X3H).
+weight-gradient tile with both fp32 operands split in-kernel (adaptseg_conv_set_option with
+ADAPTSEG_OPT_X3H / the environment variable ADAPTSEG_X3H).
 
 Same six products, per-accumulator k order and epilogue as the term-image kernel (selectors 88 /
 89) — only the operand path differs (register-gathered fp32 rows split while staged instead of
@@ -32,7 +33,7 @@ def k():
 
 
 def x3h_eligible(cin, cout, ks, stride, op):
-    """The library's x3h rule (conv_igemm.hip make_plan): K >= 512 (ADAPTSEG_X3H_MIN_K), no
+    """The library's x3h rule (conv_igemm.hip choose_x3): K >= 512 (kX3hMinK), no
     stride-2 data gradient."""
     return ks * ks * (cin if op == 0 else cout) >= 512 and not (op == 1 and stride == 2)
 
