@@ -163,18 +163,25 @@ WGRAD_STREAM = _switch("ADAPTSEG_WGRAD_STREAM", 1, (0, 1))
 # (c2 -1.1 %, c3 -1.1 %, profiles/r6/bn_fold_ab.txt: the x3h forward and the staged weight
 # gradient lose more to the in-gather BN than the apply pass cost) — off by default
 BN_FOLD = _switch("ADAPTSEG_BN_FOLD", 0, (0, 1, 2, 3))   # bit 1: BN2 -> conv3; bit 2: BN1 -> conv2
-_FOLD_OK: dict = {}
+_PLANNED: dict = {}
+
+
+def _planned(fn, *args):
+    """fn(*args) — a planner query, or a plan made of them — cached on its arguments and on what
+    else the answer depends on, all read now: the conv maths, both kernel options (set_x3h,
+    set_g16_wide) and the engine's switches."""
+    key = (fn, args, K.get_conv_math(), K.get_x3h(), K.get_g16_wide(), BF16_GRADS, BN_FOLD, BN_SUMS, MASK_BITS,
+           X3_FWD_TERMS, X3_BWD_TERMS, X3_WGRAD_TERMS_MIN_C)
+    if key not in _PLANNED:
+        _PLANNED[key] = fn(*args)
+    return _PLANNED[key]
 
 
 def _fold_ok(g, n, h, w) -> bool:
     """conv ``g`` on an n x h x w input can take its operand BN in the forward (with fused
     output statistics) and the weight gradient."""
-    key = (g, n, h, w, K.get_conv_math(), K.get_x3h())
-    v = _FOLD_OK.get(key)
-    if v is None:
-        v = _FOLD_OK[key] = (K.operand_bn_ok(g, n, h, w, 0) and K.operand_bn_ok(g, n, h, w, 2) and
-                             K.conv_bnstats_tiles(g, n, h, w, K.nhwc_strides(n, h, w, g.cin)) > 0)
-    return v
+    return (K.operand_bn_ok(g, n, h, w, 0) and K.operand_bn_ok(g, n, h, w, 2) and
+            K.conv_bnstats_tiles(g, n, h, w, K.nhwc_strides(n, h, w, g.cin)) > 0)
 
 
 def lowp_grads() -> bool:
@@ -186,21 +193,11 @@ def lowp_grads() -> bool:
     return lowp_storage() and BF16_GRADS == 1
 
 
-_BF16_SEL: dict = {}
-
-
 def bf16_only(g, n, h, w, ops) -> bool:
     """True when every listed product of this conv runs on a kernel that reads only the bf16
     copy of its activation operand (the LDS-DMA kernels; the library's own plan,
     adaptseg_conv2d_copy_operand_only): the fp32 tensor then need not be written at all."""
-    for op in ops:
-        key = (g, n, h, w, op, K.get_conv_math())
-        v = _BF16_SEL.get(key)
-        if v is None:
-            v = _BF16_SEL[key] = K.conv_copy_operand_only(g, n, h, w, op)
-        if not v:
-            return False
-    return True
+    return all(_planned(K.conv_copy_operand_only, g, n, h, w, op) for op in ops)
 
 
 def _copy_pays(g, n, h, w, ops) -> bool:
@@ -209,48 +206,37 @@ def _copy_pays(g, n, h, w, ops) -> bool:
     return any(bf16_only(g, n, h, w, (op,)) for op in ops)
 
 
-def bn_forward_b(bn, x, res, relu, training, tiles=None, bf16=False, fp32=True, ybits=None):
-    """bn_forward that also returns the bf16 copy of y (None unless ``bf16``); fp32=False skips
-    the fp32 y (returned as None) when every consumer reads the copy.  ybits: a mask_bits_like
-    bitmap the pass fills with y's ReLU mask."""
-    fp32 = fp32 or not bf16
+def bn_forward(bn, x, res, relu, training, tiles=None, bf16=False, fp32=True, ybits=None):
+    """-> (y, the statistics bn_backward takes, the operand copy of y or None).  tiles: row-tile
+    statistics of x from the producing conv (conv_fwd_bnstats), which replace the BN's own statistics
+    pass in train mode.  bf16: also write the operand copy of y; fp32=False (with it) skips the fp32 y
+    (None) when every consumer reads the copy.  ybits: a mask_bits_like bitmap the pass fills with
+    y's ReLU mask."""
     if training:
-        if tiles is not None:
-            r = K.bn_fwd_train_tiles(x, tiles, bn.weight, bn.bias, bn.running_mean, bn.running_var,
-                                     bn.momentum, bn.eps, res=res, relu=relu, bf16_out=bf16, fp32_out=fp32,
-                                     ybits=ybits)
-        else:
-            r = K.bn_fwd_train(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum,
-                               bn.eps, res=res, relu=relu, bf16_out=bf16, fp32_out=fp32, ybits=ybits)
-        y, mean, invstd = r[:3]
-        return y, (mean, invstd, True), (r[3] if bf16 else None)
-    r = K.bn_fwd_infer(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, res=res,
-                       relu=relu, bf16_out=bf16, fp32_out=fp32, ybits=ybits)
-    y, yb = r if bf16 else (r, None)
+        y, mean, invstd, yb = K.bn_fwd_train_all(x, tiles, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                                                 bn.momentum, bn.eps, res=res, relu=relu, bf16_out=bf16,
+                                                 fp32_out=fp32, ybits=ybits)
+        return y, (mean, invstd, True), yb
+    y, yb = K.bn_fwd_infer_all(x, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps, res=res,
+                               relu=relu, bf16_out=bf16, fp32_out=fp32, ybits=ybits)
     return y, (bn.running_mean, None, False), yb
-
-
-def bn_forward(bn, x, res, relu, training, tiles=None):
-    """tiles: row-tile statistics of x from the producing conv (conv_fwd_bnstats), which
-    replace the BN's own statistics pass in train mode."""
-    y, st, _ = bn_forward_b(bn, x, res, relu, training, tiles)
-    return y, st
 
 
 def bn_backward(bn, dy, y, x, st, relu, dx=None, dres=None, mask_from_x=False, bf16=False, fp32=True,
                 dybits=None, sums=None):
     """mask_from_x: a BN+ReLU without residual recomputes its ReLU mask from x in train
     mode instead of reading the saved output y (one activation read less per pass).
-    bf16: return (dx, bf16 copy of dx) for the bf16-math data gradient that consumes dx.
+    Returns (dx, dxb): dxb is the operand copy of dx for the data gradient that consumes it (``bf16``;
+    else None), dx is None when only the copy is written (fp32=False).
     dybits: a mask bitmap applied to dy first (the Bottleneck's BN3 / downsample BN).
-    sums: the backward sums the producing data gradient fused (bn_sums_spec), or None."""
+    sums: the backward sums the producing data gradient fused (_dgrad(bnsum=...)), or None."""
     mean, invstd, train = st
     if not train:  # eval-mode backward needs 1/sqrt(var+eps) of the running statistics
         invstd = torch.rsqrt(bn.running_var + bn.eps)
     elif mask_from_x and relu:
         y = None
-    return K.bn_bwd(dy, y, x, bn.weight, mean, invstd, relu=relu, dx=dx, dres=dres, train=train,
-                    bias=bn.bias, bf16_out=bf16, fp32_out=fp32 or not bf16, dybits=dybits, sums=sums)
+    return K.bn_bwd_all(dy, y, x, bn.weight, mean, invstd, relu=relu, dx=dx, dres=dres, train=train,
+                        bias=bn.bias, bf16_out=bf16, fp32_out=fp32, dybits=dybits, sums=sums)
 
 
 # (A/B switch) the BN backward reduction of a Bottleneck's BN1 / BN2 fused into the epilogue of the
@@ -265,13 +251,12 @@ def bn_backward(bn, dy, y, x, st, relu, dx=None, dres=None, mask_from_x=False, b
 BN_SUMS = _switch("ADAPTSEG_BN_SUMS", 0, (0, 1, 2, 3))
 
 
-def bn_sums_spec(bn, x, st, which=3):
-    """K.BnSum of a train-mode BN+ReLU (mask recomputed from x) for conv_dgrad(bnsum=...), or None.
-    which: the BN_SUMS bit of this BN."""
-    mean, invstd, train = st
-    if not (BN_SUMS & which and train) or lowp_grads():
-        return None
-    return K.BnSum(x, mean, invstd, bn.weight, bn.bias, K.BNSUM_RELU_X)
+def _bn_sum(bn, x, st):
+    """K.BnSum of a train-mode BN+ReLU (mask recomputed from x) for _dgrad(bnsum=...)."""
+    return K.BnSum(x, st[0], st[1], bn.weight, bn.bias, K.BNSUM_RELU_X)
+
+
+_dgrad = K.conv_dgrad_all   # a data gradient whose copy or sums may be wanted: always (dx, dxb, sums)
 
 
 # ---------------------------------------------------------------------------------------
@@ -280,12 +265,17 @@ def bn_sums_spec(bn, x, st, which=3):
 
 
 class BlockRec:
-    __slots__ = ("x", "c1", "y1", "s1", "c2", "y2", "s2", "c3", "s3", "out", "cd", "sd",
-                 "n", "h", "w", "oh", "ow", "xb", "y1b", "y2b", "bits3", "abn1", "abn2", "wt2")
+    """What block_forward saves for block_backward: its plan and the tensors the plan says exist
+    (out / outb: the fp32 / bf16 block output, kept only as BN3's mask source when no bitmap is)."""
+    __slots__ = ("plan", "x", "xb", "c1", "y1", "y1b", "s1", "abn1", "c2", "y2", "y2b", "s2", "abn2", "c3", "s3",
+                 "out", "outb", "bits3", "cd", "sd", "n", "h", "w", "oh", "ow")
 
 
 # (A/B switch) the Bottleneck's output ReLU mask as a bitmap (1 bit per element) instead of the
-# stored block output: BN3's backward and the residual gradient read it
+# stored block output: BN3's backward and the residual gradient read it — 1 bit per element
+# instead of re-reading the stored output (4 B) twice.  fp32 storage only: with bf16 storage the
+# output re-read costs 2 B, and the masked residual in the bf16 data-gradient epilogue measured
+# c5 -1.2 % (profiles/r4/mask_bits_ab.txt)
 MASK_BITS = _switch("ADAPTSEG_MASK_BITS", 1, (0, 1))
 
 
@@ -299,14 +289,9 @@ def _conv_plain(g, x, n, h, w, weight, strides=None, xb=None, bf16_only=False):
 
 
 def x3_forward_terms(g) -> bool:
-    """(X3_FWD_TERMS 1; off by default since round 6, the x3h tile reads the fp32 y1 instead)
-    F32X3 (default maths, no operand copies): run this conv's forward on the term-image
-    kernel (conv_x3r.hpp, 256x128x32 LDS-DMA) with the producing BN writing its input's three
-    bf16 terms beside the fp32 tensor — the dilated 3x3 conv2 of layers 3-4 (Cin >= 256).  The
-    forward runs without the weight-gradient stream beside it, so the kernel's one-block-per-CU
-    footprint costs nothing there (it does in the backward, §3.2).  Same box: c2 26.95 / 26.91
-    -> 27.33 / 27.25 images/s, c3 17.35 / 17.36 -> 17.66 / 17.66; extending it to Cin 128 / 64
-    (layers 1-2) measured no further gain (profiles/r3/x3r_forward_ab.txt)."""
+    """F32X3 (default maths, no operand copies) with X3_FWD_TERMS 1: this conv's forward runs on the
+    term-image kernel (conv_x3r.hpp, 256x128x32 LDS-DMA), the producing BN writing its input's three
+    bf16 terms beside the fp32 tensor — the dilated 3x3 conv2 of layers 3-4 (Cin >= 256)."""
     return (X3_FWD_TERMS == 1 and K.get_conv_math() == K.MATH_F32X3 and g.kh * g.kw > 1 and g.cin >= 256
             and g.cin % 32 == 0)
 
@@ -316,7 +301,11 @@ def x3_forward_terms(g) -> bool:
 # on the x3h tile over the fp32 tensors and its weight gradient on the staged kernel.  Same box:
 # c2 +1.5 % / +1.1 %, c3 +0.8 % / +0.6 % over the term-image program (two A/B runs,
 # profiles/r6/x3_terms_retune_ab.txt): x3h reads 4-B fp32 rows instead of 6-B term images and
-# BN1 / BN2's backward write no term copies
+# BN1 / BN2's backward write no term copies.  (The term-image forward's own gain, round 3: it runs
+# without the weight-gradient stream beside it, so the kernel's one-block-per-CU footprint costs
+# nothing there, as it does in the backward, §3.2 — c2 26.95 / 26.91 -> 27.33 / 27.25 images/s,
+# c3 17.35 / 17.36 -> 17.66 / 17.66; extending it to Cin 128 / 64 (layers 1-2) measured no further
+# gain, profiles/r3/x3r_forward_ab.txt.)
 X3_FWD_TERMS = _switch("ADAPTSEG_X3_FWD_TERMS", 0, (0, 1))
 
 # (A/B switch) with X3_FWD_TERMS 0: conv2 of Cin >= this (layer 4: 512) keeps its WEIGHT gradient
@@ -361,112 +350,168 @@ def out_fp32_needed(nxt, cls, n, h, w) -> bool:
     return cls is not None and not bf16_only(aspp_geom(cls), n, h, w, (0, 2))
 
 
+@dataclasses.dataclass(frozen=True)
+class Forms:
+    """The forms one tensor is stored in: fp32, the operand copy (bf16 image / F32X3 term images)."""
+    fp32: bool
+    copy: bool
+
+
+@dataclasses.dataclass(frozen=True)
+class Reads:
+    """Which products of one conv are handed the operand copies of their activation operands."""
+    fwd: bool
+    dgrad: bool
+    wgrad: bool
+
+
+@dataclasses.dataclass(frozen=True)
+class BlockPlan:
+    """The storage plan of one Bottleneck forward + backward (DESIGN.md "Block plan" lists, per
+    field, the switches and planner queries that set it).  block_forward makes it and saves it in
+    the BlockRec; block_backward reads it there."""
+    copies: bool        # bf16_operands(): every conv operand has a copy, the residual stream is one
+    lowp: bool          # lowp_storage(): conv outputs are bf16 tensors
+    lowp_grads: bool    # lowp_grads(): data gradients are bf16 tensors
+    y1: Forms           # BN1 / BN2 + ReLU outputs
+    y2: Forms
+    keep_y2: bool       # the fp32 y2 is saved (not when conv3's backward reads y2's term images)
+    res: Forms          # the downsample BN's output
+    out: Forms          # the block output
+    dc3: Forms          # BN3's / BN2's / BN1's / the downsample BN's input gradients
+    dy2: Forms
+    dy1: Forms
+    gd: Forms
+    bits3: bool         # the output's ReLU mask is saved as a bitmap instead of the output
+    fold1: bool         # BN1 / BN2 run as statistics only, folded into conv2 / conv3 (K.OperandBN)
+    fold2: bool
+    sums1: bool         # conv2's / conv3's data gradient is asked for BN1's / BN2's backward sums
+    sums2: bool
+    conv2: Reads
+    conv3: Reads
+
+
+def block_plan(geoms, n, h, w, training, save, has_xb, out_fp32) -> BlockPlan:
+    """geoms: (conv1, conv2, conv3, downsample conv or None) geometries; has_xb: the input comes
+    with an operand copy.  (block_forward asks through _planned: made once per block and setting.)"""
+    g1, g2, g3, gd = geoms
+    oh, ow = g1.out_hw(h, w)
+    sh, lp, lg = bf16_operands(), lowp_storage(), lowp_grads()
+
+    def forms(fp32, copy):   # (a tensor without a copy is always written in fp32)
+        return Forms(fp32 or not copy, copy)
+
+    def copy_only(g, hh, ww, ops, on=True):   # every listed product of g reads the copy alone
+        return sh and on and bf16_only(g, n, hh, ww, ops)
+
+    def tiles(g, hh, ww, copy):   # g's forward produces the fused BN statistics
+        return K.conv_bnstats_tiles(g, n, hh, ww, K.nhwc_strides(n, hh, ww, g.cin), with_copy=copy) > 0
+
+    # F32X3 without operand copies: the conv2 / conv3 products that run on term images
+    x3 = not sh and x3_forward_terms(g2)                         # conv2's forward
+    wt2 = not sh and save and training and x3_wgrad_terms(g2)    # conv2's weight gradient alone
+    t2 = wt2 or (x3 and save and X3_BWD_TERMS >= 1)              # conv2's weight gradient
+    d2 = t2 and not wt2 and X3_BWD_TERMS >= 2                    # ... and its data gradient
+    t3 = x3 and save and X3_BWD_TERMS >= 3 and g3.cin % 32 == 0  # conv3's backward
+    fold1 = (bool(BN_FOLD & 2) and training and not sh and not x3 and not wt2 and tiles(g1, h, w, has_xb)
+             and _fold_ok(g2, n, oh, ow))
+    fold2 = (bool(BN_FOLD & 1) and training and not sh and not t3 and (fold1 or tiles(g2, oh, ow, x3))
+             and _fold_ok(g3, n, oh, ow))
+    none = Forms(False, False)
+    return BlockPlan(
+        copies=sh, lowp=lp, lowp_grads=lg,
+        # y1 / y2 are read only by the next conv's forward and weight gradient (the BN backward
+        # recomputes its ReLU mask from x in train mode, reads the copy in eval mode)
+        y1=none if fold1 else forms(not copy_only(g2, oh, ow, (0, 2)) and (not x3 or (save and not t2)),
+                                    sh or x3 or wt2),
+        y2=none if fold2 else forms(not copy_only(g3, oh, ow, (0, 2)), sh or t3), keep_y2=not t3,
+        res=Forms(not sh, sh), out=forms(out_fp32, sh),
+        # a BN-backward output read only by copy-operand data / weight gradients: copy only
+        dc3=forms(not t3 and not copy_only(g3, oh, ow, (1, 2)), sh or t3),
+        dy2=forms(not d2 and not copy_only(g2, oh, ow, (1, 2)), sh or t2),
+        dy1=forms(not copy_only(g1, h, w, (1, 2), has_xb), sh),
+        gd=forms(gd is None or not copy_only(gd, h, w, (1, 2), has_xb), sh),
+        bits3=save and bool(MASK_BITS) and not lp and g3.cout % 32 == 0,
+        fold1=fold1, fold2=fold2,
+        sums1=bool(BN_SUMS & 2) and training and not lg, sums2=bool(BN_SUMS & 1) and training and not lg,
+        conv2=Reads(sh or x3, sh or d2, sh or t2), conv3=Reads(sh or t3, sh or t3, sh or t3))
+
+
+def _bn_fold(bn, c, tiles):
+    """A train-mode BN + ReLU folded into its consumer conv (BN_FOLD): its statistics alone, from
+    the producing conv's row tiles -> (the saved statistics, the consumer's K.OperandBN)."""
+    if tiles is None:
+        raise RuntimeError("BN_FOLD: the producing conv ran without fused statistics (an unaligned operand)")
+    mean, invstd = K.bn_fwd_train_tiles_stats(c, tiles, bn.running_mean, bn.running_var, bn.momentum, bn.eps)
+    return (mean, invstd, True), K.OperandBN(mean, invstd, bn.weight, bn.bias)
+
+
 def block_forward(blk, x, n, h, w, training, save, xb=None, out_fp32=True):
     """xb: bf16 copy of x (bf16 conv math), or None; x may be None when xb is given (bf16
     activation storage).  out_fp32: also write the fp32 block output (bf16 storage: a consumer
     reads fp32; block_input_fp32).  Returns (out or None, rec, bf16 copy of out)."""
     g1, g2, g3 = blk.conv1.geom(), blk.conv2.geom(), blk.conv3.geom()
+    down = blk.downsample
+    p = _planned(block_plan, (g1, g2, g3, down[0].geom() if down is not None else None), n, h, w, training, save,
+                 xb is not None, out_fp32)
     oh, ow = g1.out_hw(h, w)
     conv = _conv_bn if training else _conv_plain
-    sh = bf16_operands()   # operand copies (bf16 or F32X3 term images)
-    lp = lowp_storage()    # bf16 math: conv outputs stored in bf16
-    # y1 / y2 are read only by the next conv's forward and weight gradient (the BN backward
-    # recomputes its ReLU mask from x in train mode, reads the bf16 y in eval mode) — with both
-    # on bf16-operand kernels, only their bf16 copies are written
-    thin1 = sh and bf16_only(g2, n, oh, ow, (0, 2))
-    thin2 = sh and bf16_only(g3, n, oh, ow, (0, 2))
-    c1, t1 = conv(g1, x, n, h, w, blk.conv1.weight, xb=xb, bf16_only=lp)
-    terms2 = not sh and x3_forward_terms(g2)   # conv2's forward on y1's term images
-    wt2 = not sh and save and training and x3_wgrad_terms(g2)   # ... or only its weight gradient
-    # ... and its weight gradient: then no consumer reads the fp32 y1 (the BN1 backward's ReLU
-    # mask comes from x in train mode, from the terms' hi image in eval mode)
-    keep1 = terms2 and save and X3_BWD_TERMS >= 1
-    need1 = not terms2 or (save and not keep1)
-    abn1 = None
-    if ((BN_FOLD & 2) and training and not sh and not terms2 and not wt2 and t1 is not None
-            and _fold_ok(g2, n, oh, ow) and c1.is_contiguous()):
-        # BN1 folded into conv2 (BN_FOLD bit 2): statistics only, y1 never written
-        bn1 = blk.bn1
-        mean1, is1 = K.bn_fwd_train_tiles_stats(c1, t1, bn1.running_mean, bn1.running_var, bn1.momentum, bn1.eps)
-        s1 = (mean1, is1, True)
-        abn1 = K.OperandBN(mean1, is1, bn1.weight, bn1.bias)
-        y1 = y1b = None
+    c1, t1 = conv(g1, x, n, h, w, blk.conv1.weight, xb=xb, bf16_only=p.lowp)
+    y1 = y1b = abn1 = y2 = y2b = abn2 = None
+    if p.fold1:
+        s1, abn1 = _bn_fold(blk.bn1, c1, t1)
         c2, t2 = K.conv_fwd_bnstats_abn(g2, c1, abn1, n, oh, ow, [blk.conv2.weight])
     else:
-        y1, s1, y1b = bn_forward_b(blk.bn1, c1, None, True, training, t1, bf16=sh or terms2 or wt2,
-                                   fp32=not thin1 and need1)
-        c2, t2 = conv(g2, y1, n, oh, ow, blk.conv2.weight, xb=None if wt2 else y1b, bf16_only=lp)
-    # conv3's backward on term images (X3_BWD_TERMS 3): BN2 also writes y2's terms for its weight
-    # gradient (the forward still reads the fp32 y2)
-    terms3 = not sh and save and X3_BWD_TERMS >= 3 and x3_forward_terms(g2) and g3.cin % 32 == 0
-    abn2 = None
-    if ((BN_FOLD & 1) and training and not sh and not terms3 and t2 is not None and _fold_ok(g3, n, oh, ow)
-            and c2.is_contiguous()):
-        # BN2 folded into conv3 (BN_FOLD): statistics only, y2 never written
-        bn2 = blk.bn2
-        mean2, is2 = K.bn_fwd_train_tiles_stats(c2, t2, bn2.running_mean, bn2.running_var, bn2.momentum, bn2.eps)
-        s2 = (mean2, is2, True)
-        abn2 = K.OperandBN(mean2, is2, bn2.weight, bn2.bias)
-        y2 = y2b = None
+        y1, s1, y1b = bn_forward(blk.bn1, c1, None, True, training, t1, bf16=p.y1.copy, fp32=p.y1.fp32)
+        c2, t2 = conv(g2, y1, n, oh, ow, blk.conv2.weight, xb=y1b if p.conv2.fwd else None, bf16_only=p.lowp)
+    if p.fold2:
+        s2, abn2 = _bn_fold(blk.bn2, c2, t2)
         c3, t3 = K.conv_fwd_bnstats_abn(g3, c2, abn2, n, oh, ow, [blk.conv3.weight])
     else:
-        y2, s2, y2b = bn_forward_b(blk.bn2, c2, None, True, training, t2, bf16=sh or terms3, fp32=not thin2)
-        c3, t3 = conv(g3, y2, n, oh, ow, blk.conv3.weight, xb=y2b, bf16_only=lp)
+        y2, s2, y2b = bn_forward(blk.bn2, c2, None, True, training, t2, bf16=p.y2.copy, fp32=p.y2.fp32)
+        c3, t3 = conv(g3, y2, n, oh, ow, blk.conv3.weight, xb=y2b, bf16_only=p.lowp)
     cd = sd = None
-    if blk.downsample is not None:
-        dconv, dbn = blk.downsample[0], blk.downsample[1]
-        cd, td = conv(dconv.geom(), x, n, h, w, dconv.weight, xb=xb, bf16_only=lp)
-        r, sd, rb = bn_forward_b(dbn, cd, None, False, training, td, bf16=sh, fp32=not sh)
-        if sh:
-            r = rb   # the residual stream is bf16
+    if down is not None:
+        cd, td = conv(down[0].geom(), x, n, h, w, down[0].weight, xb=xb, bf16_only=p.lowp)
+        r, sd, rb = bn_forward(down[1], cd, None, False, training, td, bf16=p.res.copy, fp32=p.res.fp32)
     else:
-        r = xb if sh else x
-    # the output's ReLU mask, out > 0, as a bitmap for the backward (BN3's mask and the residual
-    # gradient's): 1 bit per element instead of re-reading the stored output (4 B / 2 B) twice
-    # (fp32 storage only: with bf16 storage the output re-read costs 2 B, and the masked residual
-    # in the bf16 data-gradient epilogue measured c5 -1.2 %, profiles/r4/mask_bits_ab.txt)
-    bits3 = K.mask_bits_like(c3) if (save and MASK_BITS and not lp and g3.cout % 32 == 0) else None
-    out, s3, outb = bn_forward_b(blk.bn3, c3, r, True, training, t3, bf16=sh, fp32=not sh or out_fp32,
-                                 ybits=bits3)
+        r, rb = x, xb
+    bits3 = K.mask_bits_like(c3) if p.bits3 else None
+    out, s3, outb = bn_forward(blk.bn3, c3, rb if p.copies else r, True, training, t3, bf16=p.out.copy,
+                               fp32=p.out.fp32, ybits=bits3)
     rec = None
     if save:
         rec = BlockRec()
-        rec.x, rec.c1, rec.y1, rec.s1, rec.c2, rec.y2, rec.s2 = x, c1, y1, s1, c2, y2, s2
-        rec.c3, rec.s3, rec.out, rec.cd, rec.sd = c3, s3, (None if bits3 is not None else out), cd, sd
-        rec.abn1, rec.abn2 = abn1, abn2
+        rec.plan, rec.n, rec.h, rec.w, rec.oh, rec.ow = p, n, h, w, oh, ow
+        rec.x, rec.xb, rec.c1, rec.s1, rec.c2, rec.s2 = x, xb, c1, s1, c2, s2
+        rec.c3, rec.s3, rec.cd, rec.sd = c3, s3, cd, sd
+        # the weight gradients' operands: y1 / y2 and their copies, or the folded BNs
+        rec.y1, rec.y1b, rec.abn1 = y1, y1b if p.conv2.wgrad else None, abn1
+        rec.y2, rec.y2b, rec.abn2 = y2 if p.keep_y2 else None, y2b, abn2
         rec.bits3 = bits3
-        rec.n, rec.h, rec.w, rec.oh, rec.ow = n, h, w, oh, ow
-        # the weight gradients' operand copies (bf16 / term images) of x, y1, y2
-        rec.xb, rec.y1b, rec.y2b = xb, y1b if (sh or keep1 or wt2) else None, y2b
-        rec.wt2 = wt2
-        if terms3:
-            rec.y2 = None   # the backward reads y2's terms (weight gradient, eval-mode mask)
-        if sh and bits3 is None:
-            rec.out = outb   # bf16 storage: the BN3 backward's mask source is the bf16 output
+        rec.out = out if not (p.bits3 or p.copies) else None
+        rec.outb = outb if p.copies and not p.bits3 else None
     return out, rec, outb
 
 
-def _wgrad(ws, g, dy, x, n, h, w, dws, dbs=None, strides=None, dyb=None, xb=None):
-    """Weight gradient of one conv: on the side stream when ``ws`` is given.  dyb / xb: bf16
-    copies of both operands (bf16 conv math)."""
-    def run():
-        K.conv_wgrad(g, dy, x, n, h, w, dws, dbs, strides=strides, dyb=dyb, xb=xb,
-                     defer=ws is not None and DEFER_SPLITK == 1)
+def _on_side(ws, run, *tensors):
+    """Run a weight gradient's launches: on the side stream when ``ws`` is given (``tensors``: what
+    they read), else inline."""
     if ws is None:
         run()
     else:
-        ws.launch(run, *[t for t in (dy, x, dyb, xb) if t is not None])
+        ws.launch(run, *[t for t in tensors if t is not None])
+
+
+def _wgrad(ws, g, dy, x, n, h, w, dws, dbs=None, strides=None, dyb=None, xb=None):
+    """Weight gradient of one conv.  dyb / xb: bf16 copies of both operands (bf16 conv math)."""
+    _on_side(ws, lambda: K.conv_wgrad(g, dy, x, n, h, w, dws, dbs, strides=strides, dyb=dyb, xb=xb,
+                                      defer=ws is not None and DEFER_SPLITK == 1), dy, x, dyb, xb)
 
 
 def _wgrad_abn(ws, g, dy, x_pre, abn, n, h, w, dws):
-    """Weight gradient whose x operand is relu(bn(x_pre)) (K.OperandBN), on the side stream when
-    ``ws`` is given."""
-    def run():
-        K.conv_wgrad_abn(g, dy, x_pre, abn, n, h, w, dws)
-    if ws is None:
-        run()
-    else:
-        ws.launch(run, *[t for t in (dy, x_pre, abn.mean, abn.invstd) if t is not None])
+    """Weight gradient whose x operand is relu(bn(x_pre)) (K.OperandBN)."""
+    _on_side(ws, lambda: K.conv_wgrad_abn(g, dy, x_pre, abn, n, h, w, dws), dy, x_pre, abn.mean, abn.invstd)
 
 
 # ---------------------------------------------------------------------------------------
@@ -495,100 +540,71 @@ def _wgrad_padded(ws, g, dy, x, n, h, w, dw, db=None):
         K.conv_wgrad(g4, dy, xp, n, h, w, [dwp], [db] if db is not None else None,
                      strides=K.nhwc_strides(n, h, w, c4))
         K.to_nhwc_pad(dwp.permute(0, 3, 1, 2)[:, :g.cin], g.cin, out=dw.permute(0, 2, 3, 1), accumulate=True)
-    if ws is None:
-        run()
-    else:
-        ws.launch(run, dy, x)
+    _on_side(ws, run, dy, x)
 
 
 def block_backward(blk, rec, gout, need_w, ws=None, dx_fp32=True):
     """gout: grad of the block output (owned, modified in place; fp32, or bf16 under bf16
     gradient storage).  Returns grad of the input — in fp32 when ``dx_fp32``, else (bf16
     gradient storage) in bf16."""
-    n, h, w, oh, ow = rec.n, rec.h, rec.w, rec.oh, rec.ow
-    g1, g2, g3 = blk.conv1.geom(), blk.conv2.geom(), blk.conv3.geom()
-    # out = relu(bn3(c3) + r): g = gout*[out>0] goes to bn3 and to the residual branch.
-    sh = bf16_operands()   # bf16 copies of each data-gradient operand (bf16 conv math)
-    # a BN-backward output read only by bf16-operand data / weight gradients: copy only
-    f3 = not (sh and bf16_only(g3, n, oh, ow, (1, 2)))
-    f2 = not (sh and bf16_only(g2, n, oh, ow, (1, 2)))
-    f1 = not (sh and rec.xb is not None and bf16_only(g1, n, h, w, (1, 2)))
-    fd = blk.downsample is None or not (sh and rec.xb is not None and
-                                        bf16_only(blk.downsample[0].geom(), n, h, w, (1, 2)))
-    # bf16 gradient storage: the data gradients are bf16 tensors; a BN backward whose fp32 output
-    # is still wanted (f*: a consumer without a bf16-operand kernel) writes it to its own buffer
-    lg = lowp_grads()
+    p, n, h, w, oh, ow = rec.plan, rec.n, rec.h, rec.w, rec.oh, rec.ow
+    c1, c2, c3 = blk.conv1, blk.conv2, blk.conv3
+    g1, g2, g3 = c1.geom(), c2.geom(), c3.geom()
+    # bf16 gradient storage: the data gradients are bf16 tensors, and a BN backward writes its fp32
+    # output (where the plan wants one) to a buffer of its own instead of in place
+    lg = p.lowp_grads
     bits = rec.bits3
-    t3 = not sh and rec.y2b is not None   # F32X3: conv3's backward on term images (X3_BWD_TERMS 3)
-    if t3:
-        f3 = False
+    # out = relu(bn3(c3) + r): g = gout*[out>0] goes to bn3 and to the residual branch.
     if bits is not None:   # g = gout * bit: BN3's input gradient; the residual gradient stays implicit
-        r = bn_backward(blk.bn3, gout, None, rec.c3, rec.s3, relu=False, dybits=bits, bf16=sh or t3, fp32=f3)
+        dc3, dc3b = bn_backward(blk.bn3, gout, None, rec.c3, rec.s3, relu=False, dybits=bits, bf16=p.dc3.copy,
+                                fp32=p.dc3.fp32)
     else:
-        r = bn_backward(blk.bn3, gout, rec.out, rec.c3, rec.s3, relu=True, dres=gout, bf16=sh or t3, fp32=f3)
-    dc3, dc3b = r if (sh or t3) else (r, None)
-    bs2 = bn_sums_spec(blk.bn2, rec.c2, rec.s2, 1)
-    r = K.conv_dgrad(g3, dc3, n, oh, ow, [blk.conv3.weight], dyb=dc3b, bf16_only=lg, bnsum=bs2)
-    dy2, sums2 = r if bs2 is not None else (r, None)
-    if need_w and blk.conv3.weight.grad is not None:
-        if rec.abn2 is not None:   # BN2 folded into conv3: its weight gradient reads c2 through BN2
-            _wgrad_abn(ws, g3, dc3, rec.c2, rec.abn2, n, oh, ow, [blk.conv3.weight.grad])
+        dc3, dc3b = bn_backward(blk.bn3, gout, rec.outb if p.copies else rec.out, rec.c3, rec.s3, relu=True,
+                                dres=gout, bf16=p.dc3.copy, fp32=p.dc3.fp32)
+    dy2, _, sums2 = _dgrad(g3, dc3, n, oh, ow, [c3.weight], dyb=dc3b, bf16_only=lg,
+                           bnsum=_bn_sum(blk.bn2, rec.c2, rec.s2) if p.sums2 else None)
+    if need_w and c3.weight.grad is not None:
+        if p.fold2:   # its weight gradient reads c2 through BN2
+            _wgrad_abn(ws, g3, dc3, rec.c2, rec.abn2, n, oh, ow, [c3.weight.grad])
         else:
-            _wgrad(ws, g3, dc3, rec.y2, n, oh, ow, [blk.conv3.weight.grad], dyb=dc3b, xb=rec.y2b)
+            _wgrad(ws, g3, dc3, rec.y2, n, oh, ow, [c3.weight.grad], dyb=dc3b, xb=rec.y2b)
     del dc3, dc3b
-    # (the saved y is the mask source in eval mode: bf16 like x under bf16 storage)
-    # F32X3 (default maths) with y1's term images saved: BN2's backward also writes dY2's terms,
-    # and conv2's weight gradient (X3_BWD_TERMS 2: its data gradient too) runs on the
-    # term-image kernel (conv_x3r.hpp) instead of splitting both fp32 operands in-kernel
-    t2 = not sh and rec.y1b is not None
-    if t2 and X3_BWD_TERMS >= 2 and not rec.wt2:   # (wt2: the data gradient reads the fp32 dY2)
-        f2 = False
-    r = bn_backward(blk.bn2, dy2, rec.y2b if (sh or rec.y2 is None) else rec.y2, rec.c2, rec.s2, relu=True,
-                    dx=None if lg else dy2,
-                    mask_from_x=True, bf16=sh or t2, fp32=f2, sums=sums2)
-    # BN2's output: in place over dy2, or (bf16 gradient storage) a new fp32 tensor / None
-    dy2, dy2b = r if (sh or t2) else (r, None)
-    if not f2:
-        dy2 = None   # not written: its consumers read dy2b
-    bs1 = bn_sums_spec(blk.bn1, rec.c1, rec.s1, 2)
-    r = K.conv_dgrad(g2, dy2, n, oh, ow, [blk.conv2.weight], dyb=dy2b if (sh or not f2) else None,
-                     bf16_only=lg, bnsum=bs1)
-    dy1, sums1 = r if bs1 is not None else (r, None)
-    if need_w and blk.conv2.weight.grad is not None:
-        if rec.abn1 is not None:   # BN1 folded into conv2: its weight gradient reads c1 through BN1
-            _wgrad_abn(ws, g2, dy2, rec.c1, rec.abn1, n, oh, ow, [blk.conv2.weight.grad])
+    # (the saved y is the BN backward's mask source in eval mode only)
+    dy2, dy2b = bn_backward(blk.bn2, dy2, rec.y2b if p.conv3.wgrad else rec.y2, rec.c2, rec.s2, relu=True,
+                            dx=None if lg else dy2, mask_from_x=True, bf16=p.dy2.copy, fp32=p.dy2.fp32, sums=sums2)
+    dy1, _, sums1 = _dgrad(g2, dy2, n, oh, ow, [c2.weight], dyb=dy2b if p.conv2.dgrad else None, bf16_only=lg,
+                           bnsum=_bn_sum(blk.bn1, rec.c1, rec.s1) if p.sums1 else None)
+    if need_w and c2.weight.grad is not None:
+        if p.fold1:   # its weight gradient reads c1 through BN1
+            _wgrad_abn(ws, g2, dy2, rec.c1, rec.abn1, n, oh, ow, [c2.weight.grad])
         else:
-            _wgrad(ws, g2, dy2, rec.y1, n, oh, ow, [blk.conv2.weight.grad], dyb=dy2b, xb=rec.y1b)
+            _wgrad(ws, g2, dy2, rec.y1, n, oh, ow, [c2.weight.grad], dyb=dy2b, xb=rec.y1b)
     del dy2, dy2b
-    r = bn_backward(blk.bn1, dy1, rec.y1b if (sh or rec.y1 is None) else rec.y1, rec.c1, rec.s1, relu=True,
-                    dx=None if lg else dy1,
-                    mask_from_x=True, bf16=sh, fp32=f1, sums=sums1)
-    dy1, dy1b = r if sh else (r, None)
-    if not f1:
-        dy1 = None
-    if need_w and blk.conv1.weight.grad is not None:
-        _wgrad(ws, g1, dy1, rec.x, n, h, w, [blk.conv1.weight.grad], dyb=dy1b, xb=rec.xb)
+    dy1, dy1b = bn_backward(blk.bn1, dy1, rec.y1 if p.y1.fp32 and not p.copies else rec.y1b, rec.c1, rec.s1,
+                            relu=True, dx=None if lg else dy1, mask_from_x=True, bf16=p.dy1.copy, fp32=p.dy1.fp32,
+                            sums=sums1)
+    if need_w and c1.weight.grad is not None:
+        _wgrad(ws, g1, dy1, rec.x, n, h, w, [c1.weight.grad], dyb=dy1b, xb=rec.xb)
     if blk.downsample is not None:
         dconv, dbn = blk.downsample[0], blk.downsample[1]
         gd = dconv.geom()
-        r = bn_backward(dbn, gout, None, rec.cd, rec.sd, relu=False, dx=None if lg else gout, bf16=sh, fp32=fd,
-                        dybits=bits)
-        goutb = r[1] if sh else None
-        gd_in = (r[0] if sh else r) if fd else None   # (gout keeps the residual gradient when not rewritten)
+        # (gout keeps the residual gradient where the plan has no fp32 form of this BN's output)
+        gd_in, goutb = bn_backward(dbn, gout, None, rec.cd, rec.sd, relu=False, dx=None if lg else gout,
+                                   bf16=p.gd.copy, fp32=p.gd.fp32, dybits=bits)
         if need_w and dconv.weight.grad is not None:
             _wgrad(ws, gd, gd_in, rec.x, n, h, w, [dconv.weight.grad], dyb=goutb, xb=rec.xb)
-        dx = K.conv_dgrad(gd, gd_in, n, h, w, [dconv.weight], dyb=goutb, bf16_only=lg and not dx_fp32)
+        dx = _dgrad(gd, gd_in, n, h, w, [dconv.weight], dyb=goutb, bf16_only=lg and not dx_fp32)[0]
         del goutb
-        K.conv_dgrad(g1, dy1, n, h, w, [blk.conv1.weight], out=dx, flags=K.EPI_ACCUMULATE, dyb=dy1b)
+        _dgrad(g1, dy1, n, h, w, [c1.weight], out=dx, flags=K.EPI_ACCUMULATE, dyb=dy1b)
     elif lg and dx_fp32 != (gout.dtype == torch.float32):
         # identity residual, bf16 gradient storage, the input gradient stored unlike gout
         dx = torch.empty((n, h, w, g1.cin), device=gout.device,
                          dtype=torch.float32 if dx_fp32 else torch.bfloat16)
-        K.conv_dgrad(g1, dy1, n, h, w, [blk.conv1.weight], out=dx, res=gout, dyb=dy1b, resbits=bits)
+        _dgrad(g1, dy1, n, h, w, [c1.weight], out=dx, res=gout, dyb=dy1b, resbits=bits)
     else:
         # identity residual: dx = dgrad(conv1) + g, written over g in place (g = gout * bit when
         # the mask is a bitmap)
-        dx = K.conv_dgrad(g1, dy1, n, h, w, [blk.conv1.weight], out=gout, res=gout, dyb=dy1b, resbits=bits)
+        dx = _dgrad(g1, dy1, n, h, w, [c1.weight], out=gout, res=gout, dyb=dy1b, resbits=bits)[0]
     return dx
 
 
@@ -616,10 +632,8 @@ def aspp_backward(cls, gy, x, n, h, w, need_w, gx_out=None, ws=None, xb=None):
     if need_w and cls.conv2d_list[0].weight.grad is not None:
         _wgrad(ws, g, gy, x, n, h, w, [c.weight.grad for c in cls.conv2d_list],
                [c.bias.grad for c in cls.conv2d_list], xb=xb)
-    if gx_out is None:
-        return K.conv_dgrad(g, gy, n, h, w, [c.weight for c in cls.conv2d_list])
     return K.conv_dgrad(g, gy, n, h, w, [c.weight for c in cls.conv2d_list], out=gx_out,
-                        flags=K.EPI_ACCUMULATE)
+                        flags=K.EPI_ACCUMULATE if gx_out is not None else 0)
 
 
 # ---------------------------------------------------------------------------------------
@@ -630,6 +644,27 @@ def aspp_backward(cls, gy, x, n, h, w, need_w, gx_out=None, ws=None, xb=None):
 def _input_strides(x):
     # (n, c, h, w) element strides of an NCHW-shaped tensor of any layout
     return tuple(x.stride())
+
+
+def _nhwc_buffer(t):
+    """An NCHW-shaped tensor autograd or a caller hands in, as a contiguous NHWC buffer."""
+    t = K.nhwc_view(t)
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _check_input(x, name, dtype=True):
+    if not x.is_cuda:
+        raise RuntimeError(f"adaptsegnet_amd {name} runs on the HIP engine only; got input on {x.device}")
+    if dtype and x.dtype != torch.float32:
+        raise RuntimeError(f"expected float32 input, got {x.dtype}")
+
+
+def _anchor_grad(model, x):
+    """(the model's autograd anchor, whether this forward saves for a backward): the anchor requires
+    grad when a parameter of the model's arena does."""
+    model._ensure_arena(x.device)
+    need_w = any(p.requires_grad for p in model._arena.params)
+    return model._anchors[need_w], torch.is_grad_enabled() and (need_w or x.requires_grad)
 
 
 class _DeeplabMultiFn(torch.autograd.Function):
@@ -645,7 +680,7 @@ class _DeeplabMultiFn(torch.autograd.Function):
         gs = model.conv1.geom()
         h0, w0 = gs.out_hw(h, w)
         c0, t0 = (_conv_bn if training else _conv_plain)(gs, x, n, h, w, model.conv1.weight, xs)
-        y0, s0 = bn_forward(model.bn1, c0, None, True, training, t0)
+        y0, s0, _ = bn_forward(model.bn1, c0, None, True, training, t0)
         p, am = K.maxpool_fwd(y0)
         ph, pw = p.shape[1], p.shape[2]
         recs = []
@@ -767,15 +802,8 @@ class _DeeplabMultiFn(torch.autograd.Function):
 def deeplab_multi_forward(model, x, input_size, first_head=True):
     """ResNetMulti.forward(x, input_size) (model/deeplab_multi.py:174-194) on the HIP engine.
     ``first_head=False``: layer5's head (ASPP + upsample) is skipped, its output None."""
-    if not x.is_cuda:
-        raise RuntimeError("adaptsegnet_amd DeeplabMulti runs on the HIP engine only; "
-                           f"got input on {x.device}")
-    if x.dtype != torch.float32:
-        raise RuntimeError(f"expected float32 input, got {x.dtype}")
-    model._ensure_arena(x.device)
-    need_w = any(p.requires_grad for p in model._arena.params)
-    grad = torch.is_grad_enabled() and (need_w or x.requires_grad)
-    anchor = model._anchors[need_w]
+    _check_input(x, "DeeplabMulti")
+    anchor, grad = _anchor_grad(model, x)
     out_w, out_h = int(input_size[0]), int(input_size[1])
     return _DeeplabMultiFn.apply(anchor, x, model, out_h, out_w, grad, bool(first_head))
 
@@ -810,9 +838,7 @@ def _disc_backward(model, acts, actsb, dims, n, gout, need_w, need_dx):
     sh = lowp_storage()   # (F32X3 term images would cost the D convs a separate copy pass)
     if need_w:
         model._arena.claim(model._pidx["all"])
-    g = K.nhwc_view(gout)
-    if not g.is_contiguous():
-        g = g.contiguous()
+    g = _nhwc_buffer(gout)
     ws = WgradStream(g.device) if need_w and WGRAD_STREAM else None
     dx, gb = None, None
     for i in reversed(range(len(convs))):
@@ -829,10 +855,9 @@ def _disc_backward(model, acts, actsb, dims, n, gout, need_w, need_dx):
             # grad wrt the previous layer's pre-activation: dgrad * leaky'(act)
             ph, pw, _ = dims[i - 1]
             nb = sh and _copy_pays(convs[i - 1].geom(), n, ph, pw, (1, 2) if need_w else (1,))
-            r = K.conv_dgrad(geo, g, n, ch, cw, [conv.weight], aux=acts[i], dyb=gb, bf16_out=nb)
-            g, gb = r if nb else (r, None)
+            g, gb, _ = _dgrad(geo, g, n, ch, cw, [conv.weight], aux=acts[i], dyb=gb, bf16_out=nb)
         elif need_dx:
-            dx = K.as_nchw(K.conv_dgrad(geo, g, n, ch, cw, [conv.weight], dyb=gb))
+            dx = K.as_nchw(_dgrad(geo, g, n, ch, cw, [conv.weight], dyb=gb)[0])
         acts[i] = actsb[i] = None
     if ws is not None:
         ws.join()
@@ -854,12 +879,11 @@ class _FCDiscriminatorFn(torch.autograd.Function):
             last = i == len(convs) - 1
             oh, ow = g.out_hw(ch, cw)
             nb = sh and not last and _copy_pays(convs[i + 1].geom(), n, oh, ow, (0, 2))
-            out = K.conv_fwd(g, cur, n, ch, cw, [conv.weight], [conv.bias], strides=cs,
-                             flags=0 if last else K.EPI_LEAKY, xb=curb, bf16_out=nb)
             dims.append((ch, cw, cs))
             acts.append(cur)
             actsb.append(curb)
-            cur, curb = out if nb else (out, None)
+            cur, curb = K.conv_fwd_all(g, cur, n, ch, cw, [conv.weight], [conv.bias], strides=cs,
+                                       flags=0 if last else K.EPI_LEAKY, xb=curb, bf16_out=nb)
             ch, cw = oh, ow
             cs = K.nhwc_strides(n, ch, cw, g.cout)
         y = K.as_nchw(cur)
@@ -901,13 +925,9 @@ class _DiscReplayFn(torch.autograd.Function):
 def discriminator_forward(model, x, keep=None):
     """FCDiscriminator.forward(x) (model/discriminator.py:27-34) on the HIP engine.  ``keep``: a
     DiscForward that receives this forward's activations for ``discriminator_replay``."""
-    if not x.is_cuda:
-        raise RuntimeError("adaptsegnet_amd FCDiscriminator runs on the HIP engine only; "
-                           f"got input on {x.device}")
-    model._ensure_arena(x.device)
-    need_w = any(p.requires_grad for p in model._arena.params)
-    grad = torch.is_grad_enabled() and (need_w or x.requires_grad)
-    return _FCDiscriminatorFn.apply(model._anchors[need_w], x, model, grad, keep)
+    _check_input(x, "FCDiscriminator", dtype=False)
+    anchor, grad = _anchor_grad(model, x)
+    return _FCDiscriminatorFn.apply(anchor, x, model, grad, keep)
 
 
 def discriminator_replay(model, keep):
@@ -961,11 +981,8 @@ class _DeeplabVGGFn(torch.autograd.Function):
             g = conv.geom()
             # the next conv's input terms: from this conv's epilogue, or from the pool after it
             want_t = vt > 0 and save and i + 1 < len(prog) and g.cout % 8 == 0 and g.cout >= VGG_TERMS_MIN_C
-            out = K.conv_fwd(g, cur, n, ch, cw, [conv.weight], [conv.bias], strides=cs,
-                             flags=K.EPI_RELU, xb=curt if vt >= 2 else None, bf16_out=want_t and not pool)
-            outt = None
-            if want_t and not pool:
-                out, outt = out
+            out, outt = K.conv_fwd_all(g, cur, n, ch, cw, [conv.weight], [conv.bias], strides=cs, flags=K.EPI_RELU,
+                                       xb=curt if vt >= 2 else None, bf16_out=want_t and not pool)
             rec = [cur, ch, cw, cs, None, curt]
             ch, cw = g.out_hw(ch, cw)
             if pool:
@@ -999,9 +1016,7 @@ class _DeeplabVGGFn(torch.autograd.Function):
         need_w = ctx.need_w
         if need_w:
             model._arena.claim(model._pidx["used"])
-        g = K.nhwc_view(gout)
-        if not g.is_contiguous():
-            g = g.contiguous()
+        g = _nhwc_buffer(gout)
         branches = model.classifier_branches()
         gc = _branches_geom(branches)
         a, ch, cw = ctx.cls_in
@@ -1012,9 +1027,8 @@ class _DeeplabVGGFn(torch.autograd.Function):
                    [b.bias.grad for b in branches])
         # grad of fc7's pre-activation: dgrad * relu'(a) (+ its term images for fc7's products)
         vt = vgg_terms()
-        r = K.conv_dgrad(gc, g, n, ch, cw, [b.weight for b in branches], aux=a,
-                         flags=K.EPI_RELU_GRAD, bf16_out=vt > 0)
-        g, gt = r if vt > 0 else (r, None)
+        g, gt, _ = _dgrad(gc, g, n, ch, cw, [b.weight for b in branches], aux=a, flags=K.EPI_RELU_GRAD,
+                          bf16_out=vt > 0)
         del a
         prog = model.conv_program()
         dx = None
@@ -1036,9 +1050,8 @@ class _DeeplabVGGFn(torch.autograd.Function):
                 # the previous conv's output-gradient terms: from this data gradient's epilogue,
                 # or from the pool's backward
                 want_t = vt > 0 and i - 1 > 0 and geo.cin % 8 == 0 and geo.cin >= VGG_TERMS_MIN_C
-                r = K.conv_dgrad(geo, g, n, ih, iw, [conv.weight], aux=xin, flags=K.EPI_RELU_GRAD,
-                                 dyb=gt if vt >= 2 else None, bf16_out=want_t and prev_pool is None)
-                g, gt = r if (want_t and prev_pool is None) else (r, None)
+                g, gt, _ = _dgrad(geo, g, n, ih, iw, [conv.weight], aux=xin, flags=K.EPI_RELU_GRAD,
+                                  dyb=gt if vt >= 2 else None, bf16_out=want_t and prev_pool is None)
                 if prev_pool is not None:
                     am, ph, pw = prev_pool
                     if want_t:
@@ -1061,15 +1074,9 @@ def _branches_geom(branches):
 
 def deeplab_vgg_forward(model, x):
     """DeeplabVGG.forward(x) (model/deeplab_vgg.py:46-49) on the HIP engine."""
-    if not x.is_cuda:
-        raise RuntimeError("adaptsegnet_amd DeeplabVGG runs on the HIP engine only; "
-                           f"got input on {x.device}")
-    if x.dtype != torch.float32:
-        raise RuntimeError(f"expected float32 input, got {x.dtype}")
-    model._ensure_arena(x.device)
-    need_w = any(p.requires_grad for p in model._arena.params)
-    grad = torch.is_grad_enabled() and (need_w or x.requires_grad)
-    return _DeeplabVGGFn.apply(model._anchors[need_w], x, model, grad)
+    _check_input(x, "DeeplabVGG")
+    anchor, grad = _anchor_grad(model, x)
+    return _DeeplabVGGFn.apply(anchor, x, model, grad)
 
 
 # ---------------------------------------------------------------------------------------
@@ -1108,7 +1115,7 @@ class _WarperFn(torch.autograd.Function):
             g = conv.geom()
             ch, cw = hw[-1]
             cc, tiles = conv_bn(g, s[-1], n, ch, cw, conv.weight)
-            y, st = bn_forward(bn, cc, None, K.ACT_LEAKY, training, tiles)
+            y, st, _ = bn_forward(bn, cc, None, K.ACT_LEAKY, training, tiles)
             s.append(y)
             cs.append(cc)
             sts.append(st)
@@ -1131,7 +1138,7 @@ class _WarperFn(torch.autograd.Function):
             ch, cw = 2 * ch, 2 * cw
             cc, tiles = conv_bn(conv.geom(), u, n, ch, cw, conv.weight)
             act = K.ACT_RELU if i == len(dec) - 1 else K.ACT_NONE
-            y, st = bn_forward(bn, cc, None, act, training, tiles)
+            y, st, _ = bn_forward(bn, cc, None, act, training, tiles)
             us.append(u)
             dcs.append(cc)
             ds.append(y)
@@ -1166,9 +1173,7 @@ class _WarperFn(torch.autograd.Function):
         dec, last = model.decoder_blocks()
         if need_w:
             model._arena.claim(_warper_pidx(model))
-        g = K.nhwc_view(gflow)
-        if not g.is_contiguous():
-            g = g.contiguous()
+        g = _nhwc_buffer(gflow)
         ws = WgradStream(g.device) if need_w and WGRAD_STREAM else None
 
         def wgrad(conv, dy, xin, hh, ww, strides=None):
@@ -1240,20 +1245,14 @@ class _WarperFn(torch.autograd.Function):
 
 def warper_forward(model, x):
     """Warper.forward(pose) (model/warper.py:263-267) on the HIP engine -> (flow, warp_list)."""
-    if not x.is_cuda:
-        raise RuntimeError("adaptsegnet_amd Warper runs on the HIP engine only; "
-                           f"got input on {x.device}")
-    if x.dtype != torch.float32:
-        raise RuntimeError(f"expected float32 input, got {x.dtype}")
+    _check_input(x, "Warper")
     depth = len(model.encoder_d.down_list) + 1
     if x.shape[2] % (1 << depth) or x.shape[3] % (1 << depth):
         raise ValueError(f"Warper: input {tuple(x.shape[2:])} must be divisible by {1 << depth} in "
                          "both dimensions (the skip connections must match; the reference fails "
                          "otherwise)")
-    model._ensure_arena(x.device)
-    need_w = any(p.requires_grad for p in model._arena.params)
-    grad = torch.is_grad_enabled() and (need_w or x.requires_grad)
-    outs = _WarperFn.apply(model._anchors[need_w], x, model, grad)
+    anchor, grad = _anchor_grad(model, x)
+    outs = _WarperFn.apply(anchor, x, model, grad)
     return outs[0], list(outs[1:])
 
 
@@ -1263,9 +1262,7 @@ class _GridWarpFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, flow, x1, x2):
         ctx.set_materialize_grads(False)
-        f = K.nhwc_view(flow)
-        if not f.is_contiguous():
-            f = f.contiguous()
+        f = _nhwc_buffer(flow)
         a1 = None if x1 is None else K.nhwc_view(x1)
         a2 = K.nhwc_view(x2)
         y1, y2 = K.grid_warp_fwd(f, a1, a2)
@@ -1276,12 +1273,8 @@ class _GridWarpFn(torch.autograd.Function):
     def backward(ctx, gy1, gy2):
         f, a1, a2 = ctx.save
         need_f, need_1, need_2 = ctx.needs_input_grad
-        g1 = None if gy1 is None or a1 is None else K.nhwc_view(gy1)
-        g2 = None if gy2 is None else K.nhwc_view(gy2)
-        if g1 is not None and not g1.is_contiguous():
-            g1 = g1.contiguous()
-        if g2 is not None and not g2.is_contiguous():
-            g2 = g2.contiguous()
+        g1 = None if gy1 is None or a1 is None else _nhwc_buffer(gy1)
+        g2 = None if gy2 is None else _nhwc_buffer(gy2)
         if g1 is None and g2 is None:
             return None, None, None
         dflow, dx1, dx2 = K.grid_warp_bwd(f, a1, a2, g1, g2, need_dflow=need_f, need_dx1=need_1,

@@ -24,7 +24,7 @@ from ._lib import (CONV_BWD_DATA, CONV_BWD_WEIGHT, CONV_FWD, EPI_ACCUMULATE, EPI
 
 __all__ = [
     "ConvGeom", "set_conv_math", "get_conv_math", "MATH_F32", "MATH_BF16", "MATH_BF16_WIDE", "MATH_F32X3", "MATH_F32X3_PRESPLIT", "conv_fwd", "conv_fwd_bnstats", "conv_dgrad", "conv_wgrad", "bn_fwd_train",
-    "bn_fwd_train_tiles", "bn_fwd_infer", "bn_bwd",
+    "bn_fwd_train_tiles", "bn_fwd_infer", "bn_bwd", "conv_fwd_all", "conv_dgrad_all", "bn_fwd_train_all", "bn_fwd_infer_all", "bn_bwd_all",
     "maxpool_fwd", "maxpool_bwd", "upsample_fwd", "upsample_bwd", "softmax_fwd", "softmax_bwd",
     "ce_fwd", "ce_bwd", "adv_fwd", "adv_bwd", "sgd_step", "adam_step", "zero_", "to_nhwc",
     "axpy", "add_i64", "weight_pack_scope", "pack_builds", "pack_count", "clear_weight_packs", "EPI_ACCUMULATE", "EPI_LEAKY", "EPI_LEAKY_GRAD", "EPI_RELU", "EPI_RELU_GRAD", "EPI_RESIDUAL",
@@ -236,32 +236,35 @@ def _wshape(g: ConvGeom):
     return (g.cout, g.cin, g.kh, g.kw)
 
 
-def conv_fwd(g: ConvGeom, x: torch.Tensor, n: int, h: int, w: int, weights, biases=None,
-             strides=None, out=None, res=None, flags: int = 0, xb=None, bf16_out: bool = False,
-             bf16_only: bool = False):
-    """y[n,oh,ow,cout] = sum_seg conv(x, w_seg) + sum_seg b_seg (+res) (EPI_LEAKY / EPI_RELU).
+def conv_fwd_all(g: ConvGeom, x: torch.Tensor, n: int, h: int, w: int, weights, biases=None,
+                 strides=None, out=None, res=None, flags: int = 0, xb=None, bf16_out: bool = False,
+                 bf16_only: bool = False):
+    """y[n,oh,ow,cout] = sum_seg conv(x, w_seg) + sum_seg b_seg (+res) (EPI_LEAKY / EPI_RELU) -> (y, yb).
     xb: optional bf16 copy of x (contiguous NHWC) for the bf16 conv math (bn_* ``bf16_out``).
-    bf16_out: also return a bf16 copy of y written by the epilogue -> (y, yb).
-    bf16_only: y stored as bf16 only (bf16 activation storage): returns the bf16 tensor."""
+    bf16_out: the epilogue also writes a bf16 copy yb of y (else yb is None).
+    bf16_only: y is stored as bf16 only (bf16 activation storage): y is the bf16 tensor, yb None."""
     strides = strides or nhwc_strides(n, h, w, g.cin)
     oh, ow = g.out_hw(h, w)
     dev = (x if x is not None else xb).device
-    if bf16_only:
-        outb = torch.empty((n, oh, ow, g.cout), device=dev, dtype=torch.bfloat16)
-        wp = _wpack(g, n, h, w, strides, weights, CONV_FWD)
-        _OP.conv2d_fwd(x, xb, list(weights), wp, list(biases) if biases is not None else [], res, None, outb,
-                       (n, g.cin, h, w), strides, _wshape(g), g.stride, g.pads, g.dils,
-                       flags | (EPI_RESIDUAL if res is not None else 0))
-        return outb
-    if out is None:
-        out = torch.empty((n, oh, ow, g.cout), device=dev, dtype=torch.float32)
     if res is not None:
         flags |= EPI_RESIDUAL
-    outb = _bf16_like(out, bf16_out)
+    if bf16_only:
+        out, outb = None, torch.empty((n, oh, ow, g.cout), device=dev, dtype=torch.bfloat16)
+    else:
+        if out is None:
+            out = torch.empty((n, oh, ow, g.cout), device=dev, dtype=torch.float32)
+        outb = _bf16_like(out, bf16_out)
     wp = _wpack(g, n, h, w, strides, weights, CONV_FWD)
     _OP.conv2d_fwd(x, xb, list(weights), wp, list(biases) if biases is not None else [], res, out, outb,
                    (n, g.cin, h, w), strides, _wshape(g), g.stride, g.pads, g.dils, flags)
-    return (out, outb) if bf16_out else out
+    return (outb, None) if bf16_only else (out, outb)
+
+
+def conv_fwd(g, x, n, h, w, weights, biases=None, strides=None, out=None, res=None, flags: int = 0, xb=None,
+             bf16_out: bool = False, bf16_only: bool = False):
+    """conv_fwd_all returning y alone, or (y, yb) with ``bf16_out``."""
+    y, yb = conv_fwd_all(g, x, n, h, w, weights, biases, strides, out, res, flags, xb, bf16_out, bf16_only)
+    return (y, yb) if bf16_out and not bf16_only else y
 
 
 def conv_bnstats_tiles(g: ConvGeom, n: int, h: int, w: int, strides, with_copy: bool = False) -> int:
@@ -367,16 +370,17 @@ class BnSum:
 BNSUM_NONE, BNSUM_RELU_X, BNSUM_BITS = 0, 1, 2
 
 
-def conv_dgrad(g: ConvGeom, dy: torch.Tensor, n: int, h: int, w: int, weights, out=None,
-               res=None, aux=None, flags: int = 0, dyb=None, bf16_out: bool = False, bf16_only: bool = False,
-               resbits=None, bnsum: BnSum | None = None):
-    """dx[n,h,w,cin] (+)= conv_transpose(dy, w) (+res) (*leaky'(aux), or relu'(aux) with EPI_RELU_GRAD).
-    bf16_out: also return a bf16 copy of dx written by the epilogue -> (dx, dxb).
+def conv_dgrad_all(g: ConvGeom, dy: torch.Tensor, n: int, h: int, w: int, weights, out=None,
+                   res=None, aux=None, flags: int = 0, dyb=None, bf16_out: bool = False, bf16_only: bool = False,
+                   resbits=None, bnsum: BnSum | None = None):
+    """dx[n,h,w,cin] (+)= conv_transpose(dy, w) (+res) (*leaky'(aux), or relu'(aux) with EPI_RELU_GRAD)
+    -> (dx, dxb, sums).
+    bf16_out: the epilogue also writes a bf16 copy dxb of dx (else dxb is None).
     bf16_only (or a bf16 ``out``): dx stored in bf16 only — bf16 gradient storage (BF16 maths);
     ``res`` may be fp32 or bf16 (adaptseg_conv2d_bwd_data_xg).  resbits: a mask bitmap
     (mask_bits_like) gating res element-wise.
-    bnsum: also compute, in the epilogue, the backward sums of that BN over dx — then the result
-    is (the usual return value, (partial, ntiles) or None when the plan cannot fuse them)."""
+    bnsum: also compute, in the epilogue, the backward sums of that BN over dx: sums is (partial,
+    ntiles), or None without ``bnsum`` or when the plan cannot fuse them."""
     low = bf16_only or (out is not None and out.dtype == torch.bfloat16)
     dev = (dy if dy is not None else dyb).device
     if out is None:
@@ -390,7 +394,6 @@ def conv_dgrad(g: ConvGeom, dy: torch.Tensor, n: int, h: int, w: int, weights, o
     outb = None if low else _bf16_like(out, bf16_out)
     dx, dxb = (None, out) if low else (out, outb)
     wp = _wpack(g, n, h, w, nhwc_strides(n, h, w, g.cin), weights, CONV_BWD_DATA)
-    ret = out if (low or not bf16_out) else (out, outb)
     nt = 0
     # the launch-time conditions of the fused sums (adaptseg_conv2d_bwd_data_bnsum): 16-B aligned
     # operands (an unaligned dY or weight downgrades the plan; the BN vectors and its fp32 x are read
@@ -402,13 +405,23 @@ def conv_dgrad(g: ConvGeom, dy: torch.Tensor, n: int, h: int, w: int, weights, o
     if nt == 0:
         _OP.conv2d_bwd_data(dy, dyb, list(weights), wp, res, resbits, aux, dx, dxb, (n, g.cin, h, w), _wshape(g),
                             g.stride, g.pads, g.dils, flags)
-        return ret if bnsum is None else (ret, None)
+        return out, outb, None
     partial = torch.empty(2 * g.cin * nt, device=dev, dtype=torch.float32)
     b = bnsum
     _OP.conv2d_bwd_data_bnsum(dy, dyb, list(weights), wp, res, resbits, dx, dxb, (n, g.cin, h, w), _wshape(g),
                               g.stride, g.pads, g.dils, flags, b.x, b.mean, b.invstd, b.weight, b.bias, b.bits,
                               int(b.mask), partial, nt)
-    return ret, (partial, nt)
+    return out, outb, (partial, nt)
+
+
+def conv_dgrad(g, dy, n, h, w, weights, out=None, res=None, aux=None, flags: int = 0, dyb=None,
+               bf16_out: bool = False, bf16_only: bool = False, resbits=None, bnsum: BnSum | None = None):
+    """conv_dgrad_all returning dx alone, or (dx, dxb) with ``bf16_out`` (fp32 storage); with ``bnsum``
+    that value and the sums as a pair."""
+    dx, dxb, sums = conv_dgrad_all(g, dy, n, h, w, weights, out, res, aux, flags, dyb, bf16_out, bf16_only, resbits,
+                                   bnsum)
+    ret = dx if dxb is None else (dx, dxb)
+    return ret if bnsum is None else (ret, sums)
 
 
 def conv_wgrad(g: ConvGeom, dy: torch.Tensor, x: torch.Tensor, n: int, h: int, w: int, dws,
@@ -471,62 +484,76 @@ def mask_bits_like(t):
     return torch.empty((t.numel() // c, c // 32), device=t.device, dtype=torch.int32)
 
 
+def _bn_out(x, out, bf16_out, fp32_out):
+    """(y, yb) of a BN apply pass over x, each None where that form is not written."""
+    y = (_f32_like(x) if out is None else out) if (fp32_out or not bf16_out) else None
+    return y, _bf16_like(x, bf16_out)
+
+
+def bn_fwd_train_all(x, tiles, weight, bias, running_mean, running_var, momentum, eps, res=None,
+                     relu=True, out=None, bf16_out=False, fp32_out=True, ybits=None):
+    """Train-mode BN apply -> (y, mean, invstd, yb).  tiles: the row-tile statistics of x from
+    conv_fwd_bnstats, which replace the statistics pass, or None.
+    bf16_out: also write yb, a bf16 (RNE) copy of y, the operand of a bf16-math conv (else None);
+    fp32_out=False (with bf16_out): only the copy is written, y is None.
+    x / res may be bf16 tensors (bf16 activation storage), both or neither.  ybits: the caller's
+    mask_bits_like(x) bitmap to fill with y's ReLU mask (or None)."""
+    y, yb = _bn_out(x, out, bf16_out, fp32_out)
+    mean, invstd = (torch.empty(x.shape[-1], device=x.device, dtype=torch.float32) for _ in range(2))
+    if tiles is None:
+        _OP.bn_fwd_train(x, weight, bias, running_mean, running_var, res, y, yb, ybits, mean, invstd,
+                         float(momentum), float(eps), int(relu))
+    else:
+        _OP.bn_fwd_train_tiles(x, tiles[0], int(tiles[1]), weight, bias, running_mean, running_var, res, y, yb,
+                               ybits, mean, invstd, float(momentum), float(eps), int(relu))
+    return y, mean, invstd, yb
+
+
 def bn_fwd_train(x, weight, bias, running_mean, running_var, momentum, eps, res=None,
                  relu=True, out=None, bf16_out=False, fp32_out=True, ybits=None):
-    """bf16_out: also return a bf16 (RNE) copy of y, the operand of a bf16-math conv: (y, mean,
-    invstd, yb).  fp32_out=False (with bf16_out): only the copy is written, y is None.
-    x / res may be bf16 tensors (bf16 activation storage), both or neither."""
-    c = x.shape[-1]
-    y = (_f32_like(x) if out is None else out) if (fp32_out or not bf16_out) else None
-    yb = _bf16_like(x, bf16_out)
-    mean = torch.empty(c, device=x.device, dtype=torch.float32)
-    invstd = torch.empty(c, device=x.device, dtype=torch.float32)
-    _OP.bn_fwd_train(x, weight, bias, running_mean, running_var, res, y, yb, ybits, mean, invstd, float(momentum),
-                     float(eps), int(relu))
-    return (y, mean, invstd, yb) if bf16_out else (y, mean, invstd)
+    """bn_fwd_train_tiles with the BN's own statistics pass."""
+    return bn_fwd_train_tiles(x, None, weight, bias, running_mean, running_var, momentum, eps, res, relu, out,
+                              bf16_out, fp32_out, ybits)
 
 
 def bn_fwd_train_tiles(x, tiles, weight, bias, running_mean, running_var, momentum, eps, res=None,
                        relu=True, out=None, bf16_out=False, fp32_out=True, ybits=None):
-    """bn_fwd_train whose statistics come from conv_fwd_bnstats's row tiles.  ybits: the caller's
-    mask_bits_like(x) bitmap to fill with y's ReLU mask (or None)."""
-    stats, ntiles = tiles
-    c = x.shape[-1]
-    y = (_f32_like(x) if out is None else out) if (fp32_out or not bf16_out) else None
-    yb = _bf16_like(x, bf16_out)
-    mean = torch.empty(c, device=x.device, dtype=torch.float32)
-    invstd = torch.empty(c, device=x.device, dtype=torch.float32)
-    _OP.bn_fwd_train_tiles(x, stats, int(ntiles), weight, bias, running_mean, running_var, res, y, yb, ybits, mean,
-                           invstd, float(momentum), float(eps), int(relu))
-    return (y, mean, invstd, yb) if bf16_out else (y, mean, invstd)
+    """bn_fwd_train_all returning (y, mean, invstd), or with ``bf16_out`` all four."""
+    r = bn_fwd_train_all(x, tiles, weight, bias, running_mean, running_var, momentum, eps, res, relu, out, bf16_out,
+                         fp32_out, ybits)
+    return r if bf16_out else r[:3]
 
 
 def bn_fwd_train_tiles_stats(x, tiles, running_mean, running_var, momentum, eps):
     """The statistics half of bn_fwd_train_tiles alone (x: the BN input, for its shape): returns
     (mean, invstd); for a BN folded into its consumer conv (OperandBN)."""
-    stats, ntiles = tiles
     c = x.shape[-1]
-    mean = torch.empty(c, device=x.device, dtype=torch.float32)
-    invstd = torch.empty(c, device=x.device, dtype=torch.float32)
-    _OP.bn_fwd_train_tiles_stats(stats, int(ntiles), x.numel() // c, c, running_mean, running_var, mean, invstd,
+    mean, invstd = (torch.empty(c, device=x.device, dtype=torch.float32) for _ in range(2))
+    _OP.bn_fwd_train_tiles_stats(tiles[0], int(tiles[1]), x.numel() // c, c, running_mean, running_var, mean, invstd,
                                  float(momentum), float(eps))
     return mean, invstd
 
 
+def bn_fwd_infer_all(x, weight, bias, running_mean, running_var, eps, res=None, relu=True, out=None,
+                     bf16_out=False, fp32_out=True, ybits=None):
+    """Eval-mode BN apply -> (y, yb), the forms as in bn_fwd_train_all."""
+    y, yb = _bn_out(x, out, bf16_out, fp32_out)
+    _OP.bn_fwd_infer(x, weight, bias, running_mean, running_var, res, y, yb, ybits, float(eps), int(relu))
+    return y, yb
+
+
 def bn_fwd_infer(x, weight, bias, running_mean, running_var, eps, res=None, relu=True, out=None,
                  bf16_out=False, fp32_out=True, ybits=None):
-    y = (_f32_like(x) if out is None else out) if (fp32_out or not bf16_out) else None
-    yb = _bf16_like(x, bf16_out)
-    _OP.bn_fwd_infer(x, weight, bias, running_mean, running_var, res, y, yb, ybits, float(eps), int(relu))
+    y, yb = bn_fwd_infer_all(x, weight, bias, running_mean, running_var, eps, res, relu, out, bf16_out, fp32_out, ybits)
     return (y, yb) if bf16_out else y
 
 
-def bn_bwd(dy, y, x, weight, mean, invstd, relu=True, dx=None, dres=None, train=True, bias=None,
-           bf16_out=False, fp32_out=True, dybits=None, sums=None):
-    """dx = BN-backward(g), g = dy*[y>0] if relu; dres receives g.  dx/dres may alias dy.
+def bn_bwd_all(dy, y, x, weight, mean, invstd, relu=True, dx=None, dres=None, train=True, bias=None,
+               bf16_out=False, fp32_out=True, dybits=None, sums=None):
+    """dx = BN-backward(g), g = dy*[y>0] if relu; dres receives g.  dx/dres may alias dy.  -> (dx, dxb).
     y=None with relu (train mode): the mask is recomputed from x, weight and bias.
     dybits: a mask bitmap (mask_bits_like) applied to dy first, g = dy * bit.
-    bf16_out: return (dx, dxb) with a bf16 (RNE) copy of dx (a bf16-math data-gradient operand);
+    bf16_out: also write dxb, a bf16 (RNE) copy of dx (a bf16-math data-gradient operand; else None);
     fp32_out=False (with bf16_out): only the copy is written, dx is None.
     sums: (partial, ntiles) from conv_dgrad(bnsum=...) over this dy (train mode): the reduction
     pass is skipped."""
@@ -539,7 +566,14 @@ def bn_bwd(dy, y, x, weight, mean, invstd, relu=True, dx=None, dres=None, train=
         _OP.bn_bwd_sums(dy, dybits, y, x, weight, bias, mean, invstd, dx, dxb, dres, int(relu), sums[0], int(sums[1]))
     else:
         _OP.bn_bwd(dy, dybits, y, x, weight, bias, mean, invstd, dx, dxb, dres, int(relu), bool(train))
-    return (dx, dxb) if bf16_out else dx
+    return dx, dxb
+
+
+def bn_bwd(dy, y, x, weight, mean, invstd, relu=True, dx=None, dres=None, train=True, bias=None,
+           bf16_out=False, fp32_out=True, dybits=None, sums=None):
+    """bn_bwd_all returning dx alone, or (dx, dxb) with ``bf16_out``."""
+    r = bn_bwd_all(dy, y, x, weight, mean, invstd, relu, dx, dres, train, bias, bf16_out, fp32_out, dybits, sums)
+    return r if bf16_out else r[0]
 
 
 ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2   # the BN entry points' activation codes

@@ -245,3 +245,49 @@ def test_inventory_counts_only_the_forwards_that_run():
     assert abs(sum(bench.conv_inventory(*args, first_head=True).values()) - base - head) <= 1e-9 * base
     multi = (model, D, "multi-level", 2, (1280, 720), (1024, 512), (1024, 512))
     assert bench.conv_inventory(*multi, first_head=True) == bench.conv_inventory(*multi)
+
+
+def test_bf16_only_asks_again_after_a_kernel_option_changes(monkeypatch):
+    """engine.bf16_only caches the library's answers; the cache keys on everything the planner's
+    answer depends on, the two kernel options (set_x3h, set_g16_wide) included, as ops.conv_desc
+    does, so a query after an option change is never answered from an entry made before it.
+
+    No geometry of the planner snapshot (tests/golden/conv_plans.json: 34 products, every maths and
+    nine option pairs) has a copy-operand-only answer that depends on the options, which is
+    asserted here from that fixture; so there is no stale answer to show, and this test pins the
+    key: the library is asked again after each option change, and not again without one."""
+    import json
+    import os
+    from adaptsegnet_amd import engine
+    from adaptsegnet_amd import kernels as K
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "conv_plans.json")) as f:
+        rows = json.load(f)
+    answers = {}
+    for math, _x3h, _wide, shape, op, *rest in rows:
+        answers.setdefault((math, shape, op), set()).add(rest[4])   # (rest[4]: copy_operand_only)
+    assert all(len(v) == 1 for v in answers.values())
+
+    asked = []
+    real = K.conv_copy_operand_only
+
+    def counting(g, n, h, w, op):
+        asked.append(op)
+        return real(g, n, h, w, op)
+    monkeypatch.setattr(K, "conv_copy_operand_only", counting)
+    g = K.ConvGeom(512, 512, 3, 3, 1, (4,), (4,))
+    saved = K.get_conv_math(), K.get_x3h(), K.get_g16_wide()
+    _bf16(K)
+    try:
+        first = engine.bf16_only(g, 2, 33, 49, (0, 1, 2))
+        n0 = len(asked)
+        assert n0 >= 1 and engine.bf16_only(g, 2, 33, 49, (0, 1, 2)) == first and len(asked) == n0
+        for setter, value in ((K.set_x3h, saved[1] ^ 7), (K.set_g16_wide, saved[2] ^ 3)):
+            setter(value)
+            n1 = len(asked)
+            again = engine.bf16_only(g, 2, 33, 49, (0, 1, 2))
+            assert len(asked) > n1, "answered from an entry cached under other options"
+            assert again == all(real(g, 2, 33, 49, op) for op in (0, 1, 2))
+    finally:
+        K.set_conv_math(saved[0])
+        K.set_x3h(saved[1])
+        K.set_g16_wide(saved[2])
