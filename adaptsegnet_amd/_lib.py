@@ -151,6 +151,11 @@ _SIGS = {
     "adaptseg_ce_workspace_size": [_L, ctypes.POINTER(_SZ)],
     "adaptseg_softmax_ce_fwd": [_L, _I, _P, _P, _I, _P, _P, _P, _SZ, _P],
     "adaptseg_softmax_ce_bwd": [_L, _I, _P, _P, _I, _P, _P, _P, _P, _I, _P],
+    "adaptseg_selfinfo_fwd": [_L, _I, _P, _P, _P],
+    "adaptseg_selfinfo_bwd": [_L, _I, _P, _P, _P, _I, _P],
+    "adaptseg_entropy_workspace_size": [_L, ctypes.POINTER(_SZ)],
+    "adaptseg_entropy_loss_fwd": [_L, _I, _P, _P, _P, _SZ, _P],
+    "adaptseg_entropy_loss_bwd": [_L, _I, _P, _P, _P, _I, _P],
     "adaptseg_adv_workspace_size": [_L, ctypes.POINTER(_SZ)],
     "adaptseg_adv_loss_fwd": [_L, _P, _F, _I, _P, _P, _SZ, _P],
     "adaptseg_adv_loss_bwd": [_L, _P, _F, _I, _P, _P, _I, _P],

@@ -594,6 +594,279 @@ __global__ void __launch_bounds__(kRowTile) ce_bwd_tiled_kernel(int64_t rows, in
 }
 
 // ------------------------------------------------------------------------------------
+// Entropy-based adaptation (ADVENT): the weighted self-information map y = -k p log p that the
+// discriminators see, and the entropy loss k * mean_rows(-sum_c p log p), k = 1 / ln C.  Per row:
+//   m = max x, d_c = x_c - m, s = sum exp(d), p_c = exp(d_c) / s, logp_c = d_c - log s,
+//   plp_c = p_c logp_c, taken as exactly 0 where p_c == 0 (underflow or x_c = -inf: 0 * -inf)
+//   map   bwd: t_c = -k dy_c (plp_c + p_c),  dx_c = t_c - p_c sum_j t_j
+//   loss  bwd: H = -sum plp,                 dx_c = -(g k / rows) (plp_c + p_c H)
+// The backwards recompute p from the logits: nothing but x (and dy) is read, so autograd keeps
+// no map alive.  Same two paths as the softmax / CE kernels: LDS tiles of kRowTile rows for
+// C <= kRowTileMaxC, one thread per global row above.  A thread's LDS row starts at word
+// tid * C and ds_read_b32 / ds_write_b32 bank 32 lanes over 32 banks: conflict-free for odd C
+// (C = 19), 2^j-way for C = 2^j * odd (2-way at C = 2, serial at C = 32) — the row passes are
+// a small part of these HBM-bound kernels, and padding the rows would cost a division per
+// element of the coalesced tile copies.
+// ------------------------------------------------------------------------------------
+__device__ __forceinline__ float plogp(float p, float logp) { return p > 0.f ? p * logp : 0.f; }
+
+// A row's statistics with its maximum taken out of the sum: j = the first maximal entry, m = x_j,
+// sr = sum_{c != j} exp(x_c - m), s = 1 + sr, inv = 1 / s, ls = log s = log1p(sr).  On a nearly
+// one-hot row (sr -> 0) log(1 + sr) would round sr away, and with it the relative accuracy of
+// logp_j = -ls, the entry that then carries the row (a lone such row: 7e-6 off fp64 with
+// log(s), 1e-7 with log1p(sr)).
+struct RowStat {
+  float m, inv, ls;
+  int j;
+};
+
+__device__ __forceinline__ RowStat row_stat(const float *v, int C) {
+  RowStat st;
+  st.m = -INFINITY;
+  st.j = 0;
+  for (int c = 0; c < C; ++c)
+    if (v[c] > st.m) {
+      st.m = v[c];
+      st.j = c;
+    }
+  float sr = 0.f;
+  for (int c = 0; c < C; ++c)
+    if (c != st.j) sr += __expf(v[c] - st.m);
+  st.inv = 1.f / (1.f + sr);
+  st.ls = log1pf(sr);
+  return st;
+}
+
+// dst (+)= v with the sum rounded on its own: an accumulating launch gives the bits of a plain
+// launch followed by an addition (no multiply of v's expression is fused into the add).
+__device__ __forceinline__ void put(float *dst, float v, int accumulate) {
+#pragma clang fp contract(off)
+  *dst = accumulate ? *dst + v : v;
+}
+
+__global__ void selfinfo_fwd_kernel(int64_t rows, int C, float nk, const float *__restrict__ x,
+                                    float *__restrict__ y) {
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    const float *xr = x + r * C;
+    const RowStat st = row_stat(xr, C);
+    const float m = st.m, inv = st.inv, ls = st.ls;
+    float *yr = y + r * C;
+    for (int c = 0; c < C; ++c) {
+      const float d = xr[c] - m;
+      yr[c] = nk * plogp(__expf(d) * inv, d - ls);
+    }
+  }
+}
+
+__global__ void selfinfo_bwd_kernel(int64_t rows, int C, float nk, const float *__restrict__ x,
+                                    const float *__restrict__ dy, float *dx, int accumulate) {
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    const float *xr = x + r * C;
+    const float *gr = dy + r * C;
+    const RowStat st = row_stat(xr, C);
+    const float m = st.m, inv = st.inv, ls = st.ls;
+    float sum = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float d = xr[c] - m, p = __expf(d) * inv;
+      sum += nk * gr[c] * (plogp(p, d - ls) + p);
+    }
+    float *dr = dx + r * C;
+    float rest = 0.f;   // dx sums to 0 over a row: dx_j = -(the others), see the tiled kernel
+    for (int c = 0; c < C; ++c) {
+      if (c == st.j) continue;
+      const float d = xr[c] - m, p = __expf(d) * inv;
+      const float t = nk * gr[c] * (plogp(p, d - ls) + p);
+      const float v = t - p * sum;
+      rest += v;
+      put(dr + c, v, accumulate);
+    }
+    put(dr + st.j, -rest, accumulate);
+  }
+}
+
+__global__ void __launch_bounds__(256) entropy_fwd_partial_kernel(int64_t rows, int C, const float *__restrict__ x,
+                                                                  float *partial) {
+  float num = 0.f;
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    const float *xr = x + r * C;
+    const RowStat st = row_stat(xr, C);
+    const float m = st.m, inv = st.inv, ls = st.ls;
+    float h = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float d = xr[c] - m;
+      h -= plogp(__expf(d) * inv, d - ls);
+    }
+    num += h;
+  }
+  __shared__ float sn[256];
+  sn[threadIdx.x] = num;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (threadIdx.x < o) sn[threadIdx.x] += sn[threadIdx.x + o];
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    partial[2 * blockIdx.x] = sn[0];
+    partial[2 * blockIdx.x + 1] = 0.f;
+  }
+}
+
+// kr = k / rows
+__global__ void entropy_bwd_kernel(int64_t rows, int C, float kr, const float *__restrict__ x,
+                                   const float *__restrict__ grad_loss, float *dx, int accumulate) {
+  const float coef = -grad_loss[0] * kr;
+  for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows;
+       r += (int64_t)gridDim.x * blockDim.x) {
+    const float *xr = x + r * C;
+    const RowStat st = row_stat(xr, C);
+    const float m = st.m, inv = st.inv, ls = st.ls;
+    float h = 0.f;
+    for (int c = 0; c < C; ++c) {
+      const float d = xr[c] - m;
+      h -= plogp(__expf(d) * inv, d - ls);
+    }
+    float *dr = dx + r * C;
+    for (int c = 0; c < C; ++c) {
+      const float d = xr[c] - m, p = __expf(d) * inv;
+      put(dr + c, coef * (plogp(p, d - ls) + p * h), accumulate);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(kRowTile) selfinfo_fwd_tiled_kernel(int64_t rows, int C, float nk,
+                                                                   const float *__restrict__ x,
+                                                                   float *__restrict__ y) {
+  extern __shared__ float sm[];
+  for (int64_t r0 = (int64_t)blockIdx.x * kRowTile; r0 < rows; r0 += (int64_t)gridDim.x * kRowTile) {
+    const int nr = (int)min<int64_t>(kRowTile, rows - r0);
+    const int n = nr * C;
+    tile_load(sm, x + r0 * C, n);
+    __syncthreads();
+    if ((int)threadIdx.x < nr) {
+      float *v = sm + threadIdx.x * C;
+      const RowStat st = row_stat(v, C);
+      const float m = st.m, inv = st.inv, ls = st.ls;
+      for (int c = 0; c < C; ++c) {
+        const float d = v[c] - m;
+        v[c] = nk * plogp(__expf(d) * inv, d - ls);
+      }
+    }
+    __syncthreads();
+    tile_store(y + r0 * C, sm, n, 0);
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(kRowTile) selfinfo_bwd_tiled_kernel(int64_t rows, int C, float nk,
+                                                                   const float *__restrict__ x,
+                                                                   const float *__restrict__ dy, float *dx,
+                                                                   int accumulate) {
+  extern __shared__ float sm[];
+  float *sg = sm + kRowTile * C;
+  for (int64_t r0 = (int64_t)blockIdx.x * kRowTile; r0 < rows; r0 += (int64_t)gridDim.x * kRowTile) {
+    const int nr = (int)min<int64_t>(kRowTile, rows - r0);
+    const int n = nr * C;
+    tile_load(sm, x + r0 * C, n);
+    tile_load(sg, dy + r0 * C, n);
+    __syncthreads();
+    if ((int)threadIdx.x < nr) {
+      float *v = sm + threadIdx.x * C;
+      float *gv = sg + threadIdx.x * C;
+      const RowStat st = row_stat(v, C);
+      const float m = st.m, inv = st.inv, ls = st.ls;
+      float sum = 0.f;
+      for (int c = 0; c < C; ++c) {   // v <- p, gv <- t
+        const float d = v[c] - m, p = __expf(d) * inv;
+        const float t = nk * gv[c] * (plogp(p, d - ls) + p);
+        v[c] = p;
+        gv[c] = t;
+        sum += t;
+      }
+      // dx sums to 0 over a row (the softmax Jacobian), so the maximal entry is minus the others:
+      // t_j - p_j * sum cancels to the last bits on a nearly one-hot row (p_j -> 1), where dx_j
+      // is of the others' size
+      float rest = 0.f;
+      for (int c = 0; c < C; ++c) {
+        const float d = gv[c] - v[c] * sum;
+        v[c] = d;
+        rest += c == st.j ? 0.f : d;
+      }
+      v[st.j] = -rest;
+    }
+    __syncthreads();
+    tile_store(dx + r0 * C, sm, n, accumulate);
+    __syncthreads();
+  }
+}
+
+__global__ void __launch_bounds__(kRowTile) entropy_fwd_tiled_kernel(int64_t rows, int C, const float *__restrict__ x,
+                                                                  float *partial) {
+  extern __shared__ float sm[];
+  __shared__ float sn[kRowTile / 64];
+  float num = 0.f;
+  for (int64_t r0 = (int64_t)blockIdx.x * kRowTile; r0 < rows; r0 += (int64_t)gridDim.x * kRowTile) {
+    const int nr = (int)min<int64_t>(kRowTile, rows - r0);
+    tile_load(sm, x + r0 * C, nr * C);
+    __syncthreads();
+    if ((int)threadIdx.x < nr) {
+      const float *v = sm + threadIdx.x * C;
+      const RowStat st = row_stat(v, C);
+      const float m = st.m, inv = st.inv, ls = st.ls;
+      float h = 0.f;
+      for (int c = 0; c < C; ++c) {
+        const float d = v[c] - m;
+        h -= plogp(__expf(d) * inv, d - ls);
+      }
+      num += h;
+    }
+    __syncthreads();
+  }
+  for (int o = 32; o > 0; o >>= 1) num += __shfl_xor(num, o);
+  if ((threadIdx.x & 63) == 0) sn[threadIdx.x >> 6] = num;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float a = 0.f;
+    for (int i = 0; i < kRowTile / 64; ++i) a += sn[i];
+    partial[2 * blockIdx.x] = a;
+    partial[2 * blockIdx.x + 1] = 0.f;
+  }
+}
+
+__global__ void __launch_bounds__(kRowTile) entropy_bwd_tiled_kernel(int64_t rows, int C, float kr,
+                                                                  const float *__restrict__ x,
+                                                                  const float *__restrict__ grad_loss, float *dx,
+                                                                  int accumulate) {
+  extern __shared__ float sm[];
+  const float coef = -grad_loss[0] * kr;
+  for (int64_t r0 = (int64_t)blockIdx.x * kRowTile; r0 < rows; r0 += (int64_t)gridDim.x * kRowTile) {
+    const int nr = (int)min<int64_t>(kRowTile, rows - r0);
+    const int n = nr * C;
+    tile_load(sm, x + r0 * C, n);
+    __syncthreads();
+    if ((int)threadIdx.x < nr) {
+      float *v = sm + threadIdx.x * C;
+      const RowStat st = row_stat(v, C);
+      const float m = st.m, inv = st.inv, ls = st.ls;
+      float h = 0.f;
+      for (int c = 0; c < C; ++c) {
+        const float d = v[c] - m;
+        h -= plogp(__expf(d) * inv, d - ls);
+      }
+      for (int c = 0; c < C; ++c) {
+        const float d = v[c] - m, p = __expf(d) * inv;
+        v[c] = coef * (plogp(p, d - ls) + p * h);
+      }
+    }
+    __syncthreads();
+    tile_store(dx + r0 * C, sm, n, accumulate);
+    __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------------------
 // Adversarial losses vs constant target t.
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ float adv_elem(float x, float t, int kind) {
@@ -1275,6 +1548,78 @@ int adaptseg_softmax_ce_bwd(int64_t rows, int c, const float *logits, const int6
                                                                (flags & ADAPTSEG_EPI_ACCUMULATE) ? 1 : 0);
   timing_end(slot, as_stream(stream));
   AS_CHECK_LAUNCH("ce_bwd");
+  return ADAPTSEG_OK;
+}
+
+// k = 1 / ln C of the entropy ops (C >= 2, checked by the callers)
+static double inv_ln(int c) { return 1.0 / std::log((double)c); }
+
+int adaptseg_selfinfo_fwd(int64_t rows, int c, const float *x, float *y, adaptseg_stream_t stream) {
+  AS_CHECK_ARG(rows > 0 && c >= 2 && x && y, "selfinfo_fwd: bad args (rows > 0, c >= 2, non-NULL x / y)");
+  const float nk = (float)-inv_ln(c);
+  if (c <= kRowTileMaxC)
+    selfinfo_fwd_tiled_kernel<<<grid1d(rows, kRowTile, 8192), kRowTile, kRowTile * c * sizeof(float),
+                                as_stream(stream)>>>(rows, c, nk, x, y);
+  else
+    selfinfo_fwd_kernel<<<grid1d(rows), 256, 0, as_stream(stream)>>>(rows, c, nk, x, y);
+  AS_CHECK_LAUNCH("selfinfo_fwd");
+  return ADAPTSEG_OK;
+}
+
+int adaptseg_selfinfo_bwd(int64_t rows, int c, const float *x, const float *dy, float *dx, int flags,
+                          adaptseg_stream_t stream) {
+  AS_CHECK_ARG(rows > 0 && c >= 2 && x && dy && dx, "selfinfo_bwd: bad args (rows > 0, c >= 2, non-NULL x / dy / dx)");
+  const float nk = (float)-inv_ln(c);
+  const int acc = (flags & ADAPTSEG_EPI_ACCUMULATE) ? 1 : 0;
+  if (c <= kRowTileMaxC)
+    selfinfo_bwd_tiled_kernel<<<grid1d(rows, kRowTile, 8192), kRowTile, 2 * kRowTile * c * sizeof(float),
+                                as_stream(stream)>>>(rows, c, nk, x, dy, dx, acc);
+  else
+    selfinfo_bwd_kernel<<<grid1d(rows), 256, 0, as_stream(stream)>>>(rows, c, nk, x, dy, dx, acc);
+  AS_CHECK_LAUNCH("selfinfo_bwd");
+  return ADAPTSEG_OK;
+}
+
+static int entropy_parts(int64_t rows) { return grid1d(rows, kRowTile * 4, 2048); }
+
+int adaptseg_entropy_workspace_size(int64_t rows, size_t *bytes) {
+  AS_CHECK_ARG(bytes && rows > 0, "entropy_workspace_size: bad args");
+  *bytes = (size_t)entropy_parts(rows) * 2 * sizeof(float);
+  return ADAPTSEG_OK;
+}
+
+int adaptseg_entropy_loss_fwd(int64_t rows, int c, const float *x, float *loss, void *ws, size_t ws_bytes,
+                              adaptseg_stream_t stream) {
+  AS_CHECK_ARG(rows > 0 && c >= 2 && x && loss, "entropy_loss_fwd: bad args (rows > 0, c >= 2, non-NULL x / loss)");
+  const int parts = entropy_parts(rows);
+  if (!ws || ws_bytes < (size_t)parts * 2 * sizeof(float)) {
+    set_error("entropy_loss_fwd: workspace too small");
+    return ADAPTSEG_ERR_WORKSPACE;
+  }
+  hipStream_t s = as_stream(stream);
+  float *partial = reinterpret_cast<float *>(ws);
+  if (c <= kRowTileMaxC)
+    entropy_fwd_tiled_kernel<<<parts, kRowTile, kRowTile * c * sizeof(float), s>>>(rows, c, x, partial);
+  else
+    entropy_fwd_partial_kernel<<<parts, 256, 0, s>>>(rows, c, x, partial);
+  AS_CHECK_LAUNCH("entropy_fwd_partial");
+  pair_final_kernel<<<1, 64, 0, s>>>(partial, parts, loss, 1, inv_ln(c) / (double)rows);
+  AS_CHECK_LAUNCH("entropy_final");
+  return ADAPTSEG_OK;
+}
+
+int adaptseg_entropy_loss_bwd(int64_t rows, int c, const float *x, const float *grad_loss, float *dx, int flags,
+                              adaptseg_stream_t stream) {
+  AS_CHECK_ARG(rows > 0 && c >= 2 && x && grad_loss && dx,
+               "entropy_loss_bwd: bad args (rows > 0, c >= 2, non-NULL x / grad_loss / dx)");
+  const float kr = (float)(inv_ln(c) / (double)rows);
+  const int acc = (flags & ADAPTSEG_EPI_ACCUMULATE) ? 1 : 0;
+  if (c <= kRowTileMaxC)
+    entropy_bwd_tiled_kernel<<<grid1d(rows, kRowTile, 8192), kRowTile, kRowTile * c * sizeof(float),
+                               as_stream(stream)>>>(rows, c, kr, x, grad_loss, dx, acc);
+  else
+    entropy_bwd_kernel<<<grid1d(rows), 256, 0, as_stream(stream)>>>(rows, c, kr, x, grad_loss, dx, acc);
+  AS_CHECK_LAUNCH("entropy_bwd");
   return ADAPTSEG_OK;
 }
 

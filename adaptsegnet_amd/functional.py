@@ -9,6 +9,8 @@ Tensors at this boundary are NCHW-shaped, as in the reference; internally they a
   BCEWithLogitsLoss / MSELoss vs const target   train_gta2cityscapes_multi.py:542-545,620-624
   nn.Upsample(bilinear, align_corners=True)     train_gta2cityscapes_multi.py:237-238 (interp),
                                                 model/deeplab_multi.py:188-189
+Beyond the reference: ``selfinfo2d`` and ``entropy_loss2d``, the two halves of entropy-based
+adaptation (ADVENT), each fused from the logits.
 """
 from __future__ import annotations
 
@@ -43,6 +45,55 @@ def softmax2d(x: torch.Tensor) -> torch.Tensor:
     """Softmax over the channel dim of an [N, C, H, W] tensor (F.softmax's implicit dim=1)."""
     _check(x, "softmax2d")
     return _Softmax2d.apply(x)
+
+
+class _SelfInfo2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        xv = K.nhwc_view(x)
+        ctx.save_for_backward(xv)   # the logits only: the backward recomputes p from them
+        return K.as_nchw(K.selfinfo_fwd(xv))
+
+    @staticmethod
+    def backward(ctx, g):
+        (xv,) = ctx.saved_tensors
+        return K.as_nchw(K.selfinfo_bwd(xv, K.nhwc_view(g)))
+
+
+def selfinfo2d(x: torch.Tensor) -> torch.Tensor:
+    """The weighted self-information map of [N, C, H, W] logits: ``-p * log(p) / ln(C)`` per channel
+    with ``p = softmax(x, dim=1)``, each value in [0, 1/(e ln C)] (0 where p underflows) — what
+    the discriminators see under ``StepConfig.d_input="entropy"`` (ADVENT's AdvEnt).  Fused from
+    the logits in one kernel; the backward keeps nothing but the logits."""
+    _check(x, "selfinfo2d")
+    if x.dim() != 4 or x.shape[1] < 2:
+        raise RuntimeError(f"selfinfo2d: expected [N, C, H, W] logits with C >= 2, got {tuple(x.shape)}")
+    return _SelfInfo2d.apply(x)
+
+
+class _EntropyLoss2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        xv = K.nhwc_view(x)
+        ctx.save_for_backward(xv)
+        return K.entropy_fwd(xv)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (xv,) = ctx.saved_tensors
+        if g.dim() == 0:
+            g = g.reshape(1)
+        return K.as_nchw(K.entropy_bwd(xv, g.contiguous()))
+
+
+def entropy_loss2d(x: torch.Tensor) -> torch.Tensor:
+    """The entropy-minimisation loss of [N, C, H, W] logits (ADVENT's MinEnt): the mean over pixels
+    of ``-sum_c p log p``, divided by ``ln C`` (1 for a uniform prediction, 0 for a one-hot one).
+    Returns a 0-dim device tensor; deterministic (block partials + one ordered fp64 sum)."""
+    _check(x, "entropy_loss2d")
+    if x.dim() != 4 or x.shape[1] < 2:
+        raise RuntimeError(f"entropy_loss2d: expected [N, C, H, W] logits with C >= 2, got {tuple(x.shape)}")
+    return _EntropyLoss2d.apply(x)
 
 
 class _CrossEntropy2d(torch.autograd.Function):

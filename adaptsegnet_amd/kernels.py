@@ -26,7 +26,7 @@ __all__ = [
     "ConvGeom", "set_conv_math", "get_conv_math", "MATH_F32", "MATH_BF16", "MATH_BF16_WIDE", "MATH_F32X3", "MATH_F32X3_PRESPLIT", "conv_fwd", "conv_fwd_bnstats", "conv_dgrad", "conv_wgrad", "bn_fwd_train",
     "bn_fwd_train_tiles", "bn_fwd_infer", "bn_bwd", "conv_fwd_all", "conv_dgrad_all", "bn_fwd_train_all", "bn_fwd_infer_all", "bn_bwd_all",
     "maxpool_fwd", "maxpool_bwd", "upsample_fwd", "upsample_bwd", "softmax_fwd", "softmax_bwd",
-    "ce_fwd", "ce_bwd", "adv_fwd", "adv_bwd", "sgd_step", "adam_step", "zero_", "to_nhwc",
+    "ce_fwd", "ce_bwd", "selfinfo_fwd", "selfinfo_bwd", "entropy_fwd", "entropy_bwd", "adv_fwd", "adv_bwd", "sgd_step", "adam_step", "zero_", "to_nhwc",
     "axpy", "add_i64", "weight_pack_scope", "pack_builds", "pack_count", "clear_weight_packs", "EPI_ACCUMULATE", "EPI_LEAKY", "EPI_LEAKY_GRAD", "EPI_RELU", "EPI_RELU_GRAD", "EPI_RESIDUAL",
 ]
 
@@ -693,6 +693,35 @@ def ce_bwd(logits, labels, out2, grad_loss, ignore=255, class_weight=None, dl=No
         dl = torch.empty_like(logits)
     _OP.softmax_ce_bwd(logits, labels, out2, grad_loss, int(ignore), class_weight, dl, bool(accumulate))
     return dl
+
+
+def selfinfo_fwd(x):
+    """-p log p / ln C per channel of the logits x [..., C] (p = softmax(x)), x's shape."""
+    y = torch.empty_like(x)
+    _OP.selfinfo_fwd(x, y)
+    return y
+
+
+def selfinfo_bwd(x, dy, out=None, accumulate=False):
+    """The gradient of selfinfo_fwd from the logits and dy (p is recomputed, no map is read)."""
+    if out is None:
+        out = torch.empty_like(x)
+    _OP.selfinfo_bwd(x, dy, out, bool(accumulate))
+    return out
+
+
+def entropy_fwd(x):
+    """mean over rows of -sum_c p log p, / ln C, of the logits x [..., C]: a 1-element device tensor."""
+    loss = torch.empty(1, device=x.device, dtype=torch.float32)
+    _OP.entropy_loss_fwd(x, loss)
+    return loss
+
+
+def entropy_bwd(x, grad_loss, dx=None, accumulate=False):
+    if dx is None:
+        dx = torch.empty_like(x)
+    _OP.entropy_loss_bwd(x, grad_loss, dx, bool(accumulate))
+    return dx
 
 
 def adv_fwd(x, target: float, kind: int):

@@ -28,6 +28,9 @@ Reference call sites the ops stand in for (file:line in /root/reference):
   softmax_ce_*        nn.CrossEntropyLoss(ignore_index=255) / CrossEntropy2d  train:546, utils/loss.py:7-36
   adv_loss_*          BCEWithLogitsLoss / MSELoss vs a constant label  train:542-545,620-624
   sgd_step/adam_step  optim.SGD / optim.Adam            train:532-540
+Beyond the reference (``LOSS_NAMES``, registered like the rest but never part of an engine program):
+  selfinfo_*          the weighted self-information map -p log p / ln C (ADVENT's discriminator input)
+  entropy_loss_*      the entropy-minimisation loss mean(-sum_c p log p) / ln C
 """
 from __future__ import annotations
 
@@ -192,15 +195,16 @@ def _fake(*args, **kwargs):
     return None
 
 
-NAMES: list = []
+NAMES: list = []        # the ops the engine and the step's own kernels launch
+LOSS_NAMES: list = []   # ops of the optional loss terms around the step (engine=False): never in an engine program
 
 
-def _op(schema):
+def _op(schema, engine=True):
     """Define adaptseg::<schema> with the decorated function as its CUDA kernel."""
     name = schema.split("(", 1)[0]
 
     def deco(fn):
-        NAMES.append(name)
+        (NAMES if engine else LOSS_NAMES).append(name)
         LIB.define(schema)
         LIB.impl(name, fn, "CUDA")
         torch.library.register_fake(f"adaptseg::{name}", _fake, lib=LIB)
@@ -640,6 +644,46 @@ def _adv_loss_bwd(x, target, kind, grad_loss, dx, accumulate):
                                            _lib.EPI_ACCUMULATE if accumulate else 0, _stream()), "adv_loss_bwd")
 
 
+# ---- entropy-based adaptation (ADVENT): x = logits [..., c], see include/adaptseg.h -------------
+@_op("selfinfo_fwd(Tensor x, Tensor(a!) y) -> ()", engine=False)
+def _selfinfo_fwd(x, y):
+    rows, c = _rc(x)
+    n = rows * c
+    check(_lib.lib().adaptseg_selfinfo_fwd(rows, c, _pf(x, n, "selfinfo_fwd x"), _pf(y, n, "selfinfo_fwd y"),
+                                           _stream()), "selfinfo_fwd")
+
+
+@_op("selfinfo_bwd(Tensor x, Tensor dy, Tensor(a!) dx, bool accumulate) -> ()", engine=False)
+def _selfinfo_bwd(x, dy, dx, accumulate):
+    rows, c = _rc(x)
+    n = rows * c
+    check(_lib.lib().adaptseg_selfinfo_bwd(rows, c, _pf(x, n, "selfinfo_bwd x"), _pf(dy, n, "selfinfo_bwd dy"),
+                                           _pf(dx, n, "selfinfo_bwd dx"),
+                                           _lib.EPI_ACCUMULATE if accumulate else 0, _stream()), "selfinfo_bwd")
+
+
+@_op("entropy_loss_fwd(Tensor x, Tensor(a!) loss) -> ()", engine=False)
+def _entropy_loss_fwd(x, loss):
+    rows, c = _rc(x)
+    b = ctypes.c_size_t(0)
+    check(_lib.lib().adaptseg_entropy_workspace_size(rows, ctypes.byref(b)), "entropy_workspace_size")
+    wp, wsz = _ws_args(b.value, x.device)
+    check(_lib.lib().adaptseg_entropy_loss_fwd(rows, c, _pf(x, rows * c, "entropy_loss_fwd x"),
+                                               _pf(loss, 1, "entropy_loss_fwd loss"), wp, wsz, _stream()),
+          "entropy_loss_fwd")
+
+
+@_op("entropy_loss_bwd(Tensor x, Tensor grad_loss, Tensor(a!) dx, bool accumulate) -> ()", engine=False)
+def _entropy_loss_bwd(x, grad_loss, dx, accumulate):
+    rows, c = _rc(x)
+    n = rows * c
+    check(_lib.lib().adaptseg_entropy_loss_bwd(rows, c, _pf(x, n, "entropy_loss_bwd x"),
+                                               _pf(grad_loss, 1, "entropy_loss_bwd grad_loss"),
+                                               _pf(dx, n, "entropy_loss_bwd dx"),
+                                               _lib.EPI_ACCUMULATE if accumulate else 0, _stream()),
+          "entropy_loss_bwd")
+
+
 # ---- optimisers and plumbing ----------------------------------------------------------------
 @_op("sgd_step(Tensor(a!) param, Tensor grad, Tensor(b!) momentum_buffer, float lr, float momentum, "
      "float weight_decay, float grad_scale, int multiplicity, bool first_step) -> ()")
@@ -812,5 +856,5 @@ class _Overloads:
 
 
 OPS = _Overloads()
-for _n in NAMES:
+for _n in NAMES + LOSS_NAMES:
     setattr(OPS, _n, getattr(torch.ops.adaptseg, _n).default)

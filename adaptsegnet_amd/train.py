@@ -26,7 +26,9 @@ constant label tensors (:621, ...) are folded into the loss kernels, and the per
 Beyond the reference: ``StepConfig.lambda_st > 0`` adds a self-training term to the target branch,
 the cross entropy of the target prediction(s) against pseudo-labels given as a fourth batch
 element (adaptsegnet_amd/pseudo.py; the CBST / BDL stage after adaptation).  At 0, the default,
-the step is the reference's.
+the step is the reference's.  ``StepConfig.d_input="entropy"`` and ``StepConfig.lambda_ent > 0`` are the
+two halves of entropy-based adaptation (ADVENT): the discriminators see the weighted self-information
+map of a prediction instead of its softmax, and the target branch adds an entropy-minimisation loss.
 
 Data parallel (one process per GPU): every rank runs the step on its own shard, and SUM
 all-reduces of the gradient arenas replace DataParallel's gradient gather
@@ -77,6 +79,14 @@ class StepConfig:
     # labels_target: int64 [N, H, W] at the size the target prediction is upsampled to
     # (``_target_size()``), e.g. adaptsegnet_amd.pseudo.pseudo_labels.  0: the step as it was
     lambda_st: float = 0.0
+    # entropy-based adaptation (ADVENT).  d_input: what the discriminators see of a prediction,
+    # "softmax" (the reference) or "entropy", the weighted self-information map -p log p / ln C
+    # (AdvEnt; functional.selfinfo2d), at every discriminator input of the step.  lambda_ent > 0
+    # (MinEnt) adds lambda_ent * entropy_loss2d(pred_target2) to the target branch's backward
+    # (multi-level: + lambda_seg * lambda_ent * entropy_loss2d(pred_target1), lambda_st's
+    # weighting of head 1); batches keep their shape.  The defaults are the step as it was
+    d_input: str = "softmax"
+    lambda_ent: float = 0.0
     # run the target-domain generator forward (+ its D forward) on a second HIP stream while
     # the source-domain backward executes (independent: same weights, read-only, separate
     # gradient kernels); the target backward then waits for the source backward.  Results are
@@ -141,6 +151,13 @@ class AdaptSegTrainer:
             raise ValueError(f"lambda_st {cfg.lambda_st!r} (expected >= 0)")
         if cfg.lambda_st > 0 and cfg.level == "source-only":
             raise ValueError("lambda_st > 0: the self-training term belongs to the target branch of the "
+                             "single-level / multi-level steps; the source-only step has none")
+        if cfg.d_input not in ("softmax", "entropy"):
+            raise ValueError(f"unknown d_input {cfg.d_input!r} (expected 'softmax' or 'entropy')")
+        if cfg.lambda_ent < 0:
+            raise ValueError(f"lambda_ent {cfg.lambda_ent!r} (expected >= 0)")
+        if cfg.lambda_ent > 0 and cfg.level == "source-only":
+            raise ValueError("lambda_ent > 0: the entropy term belongs to the target branch of the "
                              "single-level / multi-level steps; the source-only step has none")
         if cfg.level != "source-only" and model_D2 is None:
             raise ValueError(f"{cfg.level} needs model_D2")
@@ -246,10 +263,17 @@ class AdaptSegTrainer:
     def _d_out(D, x, keep):
         return D(x) if keep is None else engine.discriminator_forward(D, x, keep=keep)
 
-    @staticmethod
-    def _d_again(D, pred, keep):
+    def _d_in(self, pred):
+        """What a discriminator sees of a prediction (cfg.d_input)."""
+        return F.selfinfo2d(pred) if self.cfg.d_input == "entropy" else F.softmax2d(pred)
+
+    def _ent_loss(self, pred_target):
+        """[entropy_loss2d(pred_target)] with lambda_ent > 0, else []."""
+        return [F.entropy_loss2d(pred_target)] if self.cfg.lambda_ent > 0 else []
+
+    def _d_again(self, D, pred, keep):
         """D on the detached target prediction for D's own step: the kept forward when there is one."""
-        return D(F.softmax2d(pred)) if keep is None else engine.discriminator_replay(D, keep)
+        return D(self._d_in(pred)) if keep is None else engine.discriminator_replay(D, keep)
 
     @staticmethod
     def _kept(*keeps):
@@ -463,16 +487,17 @@ class AdaptSegTrainer:
         def target_forward():
             with self._target_ctx(ov):
                 pt2 = self._pred_single(images_t, tsize, None if flow is None else flow.detach())
-                adv2 = F.adv_loss(self._d_out(D2, F.softmax2d(pt2), keep2), 0.0, self.kind)
-                return pt2, adv2, ([] if labels_t is None else [self._st_loss(pt2, labels_t, ov)])
+                adv2 = F.adv_loss(self._d_out(D2, self._d_in(pt2), keep2), 0.0, self.kind)
+                st = [] if labels_t is None else [self._st_loss(pt2, labels_t, ov)]
+                return pt2, adv2, st, self._ent_loss(pt2)
 
         first = ov is not None and c.target_first
         if first:
-            pred_target2, loss_adv_target2, loss_st = target_forward()
+            pred_target2, loss_adv_target2, loss_st, loss_ent = target_forward()
         self._backward([loss_seg2], [inv])
         L.add("loss_seg2", loss_seg2, inv)
         if not first:
-            pred_target2, loss_adv_target2, loss_st = target_forward()
+            pred_target2, loss_adv_target2, loss_st, loss_ent = target_forward()
 
         with self._target_ctx(ov):
             dev_ = loss_adv_target2.device
@@ -480,20 +505,23 @@ class AdaptSegTrainer:
             self._join_source(ov)
             if g_done is not None:
                 g_done.begin()
-            self._backward([loss_adv_target2] + loss_st,
-                           [c.lambda_adv_target2 * inv] + [c.lambda_st * inv] * len(loss_st))
+            self._backward([loss_adv_target2] + loss_st + loss_ent,
+                           [c.lambda_adv_target2 * inv] + [c.lambda_st * inv] * len(loss_st)
+                           + [c.lambda_ent * inv] * len(loss_ent))
             L.add("loss_adv_target2", loss_adv_target2, inv)
             for t in loss_st:
                 L.add("loss_st2", t, inv)
+            for t in loss_ent:
+                L.add("loss_ent2", t, inv)
             if g_done is not None:
                 g_done.end()
-        self._overlap_end(ov, pred_target2, loss_adv_target2, *loss_st, *self._kept(keep2))
+        self._overlap_end(ov, pred_target2, loss_adv_target2, *loss_st, *loss_ent, *self._kept(keep2))
 
         self._set_requires_grad(D2, True)
         pred2 = pred2.detach()
         pred_target2 = pred_target2.detach()
         with self._d_ctx(dfork, dev_, pred2, pred_target2, *self._kept(keep2)):
-            loss_d2 = F.adv_loss(D2(F.softmax2d(pred2)), 0.0, self.kind)
+            loss_d2 = F.adv_loss(D2(self._d_in(pred2)), 0.0, self.kind)
             self._backward([loss_d2], [inv / 2])
             L.add("loss_D2", loss_d2, inv / 2)
             loss_d2 = F.adv_loss(self._d_again(D2, pred_target2, keep2), 1.0, self.kind)
@@ -514,19 +542,19 @@ class AdaptSegTrainer:
         def target_forward():
             with self._target_ctx(ov):
                 pt1, pt2 = self.model(images_t, tsize)
-                adv1 = F.adv_loss(self._d_out(D1, F.softmax2d(pt1), keep1), 0.0, self.kind)
-                adv2 = F.adv_loss(self._d_out(D2, F.softmax2d(pt2), keep2), 0.0, self.kind)
+                adv1 = F.adv_loss(self._d_out(D1, self._d_in(pt1), keep1), 0.0, self.kind)
+                adv2 = F.adv_loss(self._d_out(D2, self._d_in(pt2), keep2), 0.0, self.kind)
                 st = [] if labels_t is None else [self._st_loss(pt1, labels_t, ov), self._st_loss(pt2, labels_t, ov)]
-                return pt1, pt2, adv1, adv2, st
+                return pt1, pt2, adv1, adv2, st, self._ent_loss(pt1) + self._ent_loss(pt2)
 
         first = ov is not None and c.target_first
         if first:
-            pred_target1, pred_target2, loss_adv1, loss_adv2, loss_st = target_forward()
+            pred_target1, pred_target2, loss_adv1, loss_adv2, loss_st, loss_ent = target_forward()
         self._backward([loss_seg2, loss_seg1], [inv, c.lambda_seg * inv])
         L.add("loss_seg1", loss_seg1, inv)
         L.add("loss_seg2", loss_seg2, inv)
         if not first:
-            pred_target1, pred_target2, loss_adv1, loss_adv2, loss_st = target_forward()
+            pred_target1, pred_target2, loss_adv1, loss_adv2, loss_st, loss_ent = target_forward()
 
         with self._target_ctx(ov):
             dev_ = loss_adv2.device
@@ -535,15 +563,18 @@ class AdaptSegTrainer:
             if g_done is not None:
                 g_done.begin()
             st_scales = [c.lambda_seg * c.lambda_st * inv, c.lambda_st * inv][:len(loss_st)]
-            self._backward([loss_adv1, loss_adv2] + loss_st,
-                           [c.lambda_adv_target1 * inv, c.lambda_adv_target2 * inv] + st_scales)
+            ent_scales = [c.lambda_seg * c.lambda_ent * inv, c.lambda_ent * inv][:len(loss_ent)]
+            self._backward([loss_adv1, loss_adv2] + loss_st + loss_ent,
+                           [c.lambda_adv_target1 * inv, c.lambda_adv_target2 * inv] + st_scales + ent_scales)
             L.add("loss_adv_target1", loss_adv1, inv)
             L.add("loss_adv_target2", loss_adv2, inv)
             for name, t in zip(("loss_st1", "loss_st2"), loss_st):
                 L.add(name, t, inv)
+            for name, t in zip(("loss_ent1", "loss_ent2"), loss_ent):
+                L.add(name, t, inv)
             if g_done is not None:
                 g_done.end()
-        self._overlap_end(ov, pred_target1, pred_target2, loss_adv1, loss_adv2, *loss_st,
+        self._overlap_end(ov, pred_target1, pred_target2, loss_adv1, loss_adv2, *loss_st, *loss_ent,
                           *self._kept(keep1, keep2))
 
         self._set_requires_grad(D1, True)
@@ -551,8 +582,8 @@ class AdaptSegTrainer:
         pred1, pred2 = pred1.detach(), pred2.detach()
         pred_target1, pred_target2 = pred_target1.detach(), pred_target2.detach()
         with self._d_ctx(dfork, dev_, pred1, pred2, pred_target1, pred_target2, *self._kept(keep1, keep2)):
-            loss_d1 = F.adv_loss(D1(F.softmax2d(pred1)), 0.0, self.kind)
-            loss_d2 = F.adv_loss(D2(F.softmax2d(pred2)), 0.0, self.kind)
+            loss_d1 = F.adv_loss(D1(self._d_in(pred1)), 0.0, self.kind)
+            loss_d2 = F.adv_loss(D2(self._d_in(pred2)), 0.0, self.kind)
             self._backward([loss_d1], [inv / 2])
             self._backward([loss_d2], [inv / 2])
             L.add("loss_D1", loss_d1, inv / 2)

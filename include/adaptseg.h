@@ -576,6 +576,27 @@ int adaptseg_softmax_ce_bwd(int64_t rows, int c, const float *logits, const int6
                             adaptseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Entropy-based adaptation (ADVENT; stands in for no reference call).  x [rows][c] logits, */
+/* p = softmax(x) per row, k = 1 / ln c, p log p taken as exactly 0 where p == 0.         */
+/*   selfinfo: y = -k p log p, the weighted self-information map the discriminators see;  */
+/*             dx = t - p * sum_j t_j with t = -k dy (p log p + p)                        */
+/*   entropy : loss[0] = k * mean_rows(H), H = -sum_c p log p (block partials in ws + one */
+/*             fixed-order fp64 finish: no float atomics, the same bits every run);       */
+/*             dx = -(grad_loss[0] k / rows) (p log p + p H), grad_loss on the device     */
+/* The backwards read only x (and dy): p is recomputed.  ADAPTSEG_EPI_ACCUMULATE: dx +=.  */
+/* Rejected on the host before any launch: c < 2 (ln c = 0), rows <= 0, a NULL pointer    */
+/* (ADAPTSEG_ERR_ARG); a NULL or short workspace (ADAPTSEG_ERR_WORKSPACE).                */
+/* ------------------------------------------------------------------------------------ */
+int adaptseg_selfinfo_fwd(int64_t rows, int c, const float *x, float *y, adaptseg_stream_t stream);
+int adaptseg_selfinfo_bwd(int64_t rows, int c, const float *x, const float *dy, float *dx,
+                          int flags, adaptseg_stream_t stream);
+int adaptseg_entropy_workspace_size(int64_t rows, size_t *bytes);
+int adaptseg_entropy_loss_fwd(int64_t rows, int c, const float *x, float *loss, void *ws,
+                              size_t ws_bytes, adaptseg_stream_t stream);
+int adaptseg_entropy_loss_bwd(int64_t rows, int c, const float *x, const float *grad_loss,
+                              float *dx, int flags, adaptseg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Adversarial losses against a constant target (train_gta2cityscapes_multi.py:542-545, */
 /* 620-624, 648-650, 668-670): kind 0 = BCEWithLogitsLoss, 1 = MSELoss, mean reduction.  */
 /* ------------------------------------------------------------------------------------ */
