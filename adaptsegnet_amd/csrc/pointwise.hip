@@ -353,9 +353,13 @@ __device__ __forceinline__ bool ce_valid(int64_t lab, int ignore, int C) {
   return lab >= 0 && lab != ignore && lab < C;
 }
 
+// PW (all four CE kernels): a weight per row, pw[r], multiplies the row's term of the numerator
+// and its gradient, not the denominator (adaptseg_softmax_ce_pw_*); !PW never reads pw.
+template <bool PW>
 __global__ void __launch_bounds__(256) ce_fwd_partial_kernel(int64_t rows, int C, const float *__restrict__ logits,
                                                              const int64_t *__restrict__ labels, int ignore,
-                                                             const float *__restrict__ cw, float *partial) {
+                                                             const float *__restrict__ cw,
+                                                             const float *__restrict__ pw, float *partial) {
   float num = 0.f, den = 0.f;
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows;
        r += (int64_t)gridDim.x * blockDim.x) {
@@ -368,7 +372,7 @@ __global__ void __launch_bounds__(256) ce_fwd_partial_kernel(int64_t rows, int C
     for (int c = 0; c < C; ++c) s += __expf(xr[c] - m);
     float nll = m + __logf(s) - xr[lab];
     float wt = cw ? cw[lab] : 1.f;
-    num += wt * nll;
+    num += PW ? pw[r] * (wt * nll) : wt * nll;
     den += wt;
   }
   __shared__ float sn[256], sd[256];
@@ -412,9 +416,11 @@ __global__ void pair_final_kernel(const float *partial, int nparts, float *out, 
   }
 }
 
+template <bool PW>
 __global__ void ce_bwd_kernel(int64_t rows, int C, const float *__restrict__ logits, const int64_t *__restrict__ labels,
-                              int ignore, const float *__restrict__ cw, const float *__restrict__ out,
-                              const float *__restrict__ grad_loss, float *dl, int accumulate) {
+                              int ignore, const float *__restrict__ cw, const float *__restrict__ pw,
+                              const float *__restrict__ out, const float *__restrict__ grad_loss, float *dl,
+                              int accumulate) {
   const float scale = grad_loss[0] / out[1];
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows;
        r += (int64_t)gridDim.x * blockDim.x) {
@@ -432,6 +438,7 @@ __global__ void ce_bwd_kernel(int64_t rows, int C, const float *__restrict__ log
     for (int c = 0; c < C; ++c) s += __expf(xr[c] - m);
     float inv = 1.f / s;
     float k = scale * (cw ? cw[lab] : 1.f);
+    if (PW) k *= pw[r];
     for (int c = 0; c < C; ++c) {
       float v = k * (__expf(xr[c] - m) * inv - (c == lab ? 1.f : 0.f));
       dr[c] = accumulate ? dr[c] + v : v;
@@ -513,9 +520,11 @@ __global__ void __launch_bounds__(kRowTile) softmax_bwd_tiled_kernel(int64_t row
   }
 }
 
+template <bool PW>
 __global__ void __launch_bounds__(kRowTile) ce_fwd_tiled_kernel(int64_t rows, int C, const float *__restrict__ logits,
                                                              const int64_t *__restrict__ labels, int ignore,
-                                                             const float *__restrict__ cw, float *partial) {
+                                                             const float *__restrict__ cw,
+                                                             const float *__restrict__ pw, float *partial) {
   extern __shared__ float sm[];
   __shared__ float sn[kRowTile / 64], sd[kRowTile / 64];
   float num = 0.f, den = 0.f;
@@ -531,7 +540,8 @@ __global__ void __launch_bounds__(kRowTile) ce_fwd_tiled_kernel(int64_t rows, in
       float s = 0.f;
       for (int c = 0; c < C; ++c) s += __expf(v[c] - m);
       const float wt = cw ? cw[lab] : 1.f;
-      num += wt * (m + __logf(s) - v[lab]);
+      const float term = wt * (m + __logf(s) - v[lab]);
+      num += PW ? pw[r0 + threadIdx.x] * term : term;
       den += wt;
     }
     __syncthreads();
@@ -556,9 +566,11 @@ __global__ void __launch_bounds__(kRowTile) ce_fwd_tiled_kernel(int64_t rows, in
   }
 }
 
+template <bool PW>
 __global__ void __launch_bounds__(kRowTile) ce_bwd_tiled_kernel(int64_t rows, int C, const float *__restrict__ logits,
                                                              const int64_t *__restrict__ labels, int ignore,
-                                                             const float *__restrict__ cw, const float *__restrict__ out,
+                                                             const float *__restrict__ cw,
+                                                             const float *__restrict__ pw, const float *__restrict__ out,
                                                              const float *__restrict__ grad_loss, float *dl,
                                                              int accumulate) {
   extern __shared__ float sm[];
@@ -582,8 +594,9 @@ __global__ void __launch_bounds__(kRowTile) ce_bwd_tiled_kernel(int64_t rows, in
           v[c] = e;
           s += e;
         }
-        const float k = scale * (cw ? cw[lab] : 1.f) / s;
-        const float kl = scale * (cw ? cw[lab] : 1.f);
+        float kl = scale * (cw ? cw[lab] : 1.f);
+        if (PW) kl *= pw[r0 + threadIdx.x];
+        const float k = kl / s;
         for (int c = 0; c < C; ++c) v[c] = v[c] * k - (c == lab ? kl : 0.f);
       }
     }
@@ -1507,24 +1520,31 @@ int adaptseg_ce_workspace_size(int64_t rows, size_t *bytes) {
   return ADAPTSEG_OK;
 }
 
-int adaptseg_softmax_ce_fwd(int64_t rows, int c, const float *logits, const int64_t *labels, int ignore,
-                            const float *class_weight, float *out, void *ws, size_t ws_bytes,
-                            adaptseg_stream_t stream) {
-  AS_CHECK_ARG(rows > 0 && c > 0 && logits && labels && out, "softmax_ce_fwd: bad args");
+// pw == nullptr: the plain forms; else the pixel-weighted ones (the PW kernels)
+static int ce_fwd_launch(const char *name, int64_t rows, int c, const float *logits, const int64_t *labels,
+                         int ignore, const float *class_weight, const float *pw, float *out, void *ws,
+                         size_t ws_bytes, adaptseg_stream_t stream) {
   int parts = ce_parts(rows);
   if (!ws || ws_bytes < (size_t)parts * 2 * sizeof(float)) {
-    set_error("softmax_ce_fwd: workspace too small");
+    set_error("%s: workspace too small", name);
     return ADAPTSEG_ERR_WORKSPACE;
   }
   hipStream_t s = as_stream(stream);
   float *partial = reinterpret_cast<float *>(ws);
-  int slot;  // logits + int64 labels
-  timing_begin(kTCeFwd, s, 4.0 * rows * c + 8.0 * rows, &slot);
-  if (c <= kRowTileMaxC)
-    ce_fwd_tiled_kernel<<<parts, kRowTile, kRowTile * c * sizeof(float), s>>>(rows, c, logits, labels, ignore,
-                                                                            class_weight, partial);
-  else
-    ce_fwd_partial_kernel<<<parts, 256, 0, s>>>(rows, c, logits, labels, ignore, class_weight, partial);
+  int slot;  // logits + int64 labels (+ the pixel weights)
+  timing_begin(kTCeFwd, s, 4.0 * rows * c + (pw ? 12.0 : 8.0) * rows, &slot);
+  const size_t lds = kRowTile * c * sizeof(float);
+  if (c <= kRowTileMaxC) {
+    if (pw) ce_fwd_tiled_kernel<true><<<parts, kRowTile, lds, s>>>(rows, c, logits, labels, ignore, class_weight, pw,
+                                                                   partial);
+    else ce_fwd_tiled_kernel<false><<<parts, kRowTile, lds, s>>>(rows, c, logits, labels, ignore, class_weight, pw,
+                                                                 partial);
+  } else {
+    if (pw) ce_fwd_partial_kernel<true><<<parts, 256, 0, s>>>(rows, c, logits, labels, ignore, class_weight, pw,
+                                                              partial);
+    else ce_fwd_partial_kernel<false><<<parts, 256, 0, s>>>(rows, c, logits, labels, ignore, class_weight, pw,
+                                                            partial);
+  }
   AS_CHECK_LAUNCH("ce_fwd_partial");
   pair_final_kernel<<<1, 64, 0, s>>>(partial, parts, out, 0, 1.0);
   timing_end(slot, s);
@@ -1532,23 +1552,63 @@ int adaptseg_softmax_ce_fwd(int64_t rows, int c, const float *logits, const int6
   return ADAPTSEG_OK;
 }
 
+static int ce_bwd_launch(int64_t rows, int c, const float *logits, const int64_t *labels, int ignore,
+                         const float *class_weight, const float *pw, const float *out, const float *grad_loss,
+                         float *dlogits, int flags, adaptseg_stream_t stream) {
+  hipStream_t s = as_stream(stream);
+  const int acc = (flags & ADAPTSEG_EPI_ACCUMULATE) ? 1 : 0;
+  int slot;  // logits + labels (+ the pixel weights) in, dlogits out
+  timing_begin(kTCeBwd, s, 8.0 * rows * c + (pw ? 12.0 : 8.0) * rows, &slot);
+  if (c <= kRowTileMaxC) {
+    const int grid = grid1d(rows, kRowTile, 8192);
+    const size_t lds = kRowTile * c * sizeof(float);
+    if (pw) ce_bwd_tiled_kernel<true><<<grid, kRowTile, lds, s>>>(rows, c, logits, labels, ignore, class_weight, pw,
+                                                                  out, grad_loss, dlogits, acc);
+    else ce_bwd_tiled_kernel<false><<<grid, kRowTile, lds, s>>>(rows, c, logits, labels, ignore, class_weight, pw,
+                                                                out, grad_loss, dlogits, acc);
+  } else {
+    if (pw) ce_bwd_kernel<true><<<grid1d(rows), 256, 0, s>>>(rows, c, logits, labels, ignore, class_weight, pw, out,
+                                                             grad_loss, dlogits, acc);
+    else ce_bwd_kernel<false><<<grid1d(rows), 256, 0, s>>>(rows, c, logits, labels, ignore, class_weight, pw, out,
+                                                           grad_loss, dlogits, acc);
+  }
+  timing_end(slot, s);
+  AS_CHECK_LAUNCH("ce_bwd");
+  return ADAPTSEG_OK;
+}
+
+int adaptseg_softmax_ce_fwd(int64_t rows, int c, const float *logits, const int64_t *labels, int ignore,
+                            const float *class_weight, float *out, void *ws, size_t ws_bytes,
+                            adaptseg_stream_t stream) {
+  AS_CHECK_ARG(rows > 0 && c > 0 && logits && labels && out, "softmax_ce_fwd: bad args");
+  return ce_fwd_launch("softmax_ce_fwd", rows, c, logits, labels, ignore, class_weight, nullptr, out, ws, ws_bytes,
+                       stream);
+}
+
 int adaptseg_softmax_ce_bwd(int64_t rows, int c, const float *logits, const int64_t *labels, int ignore,
                             const float *class_weight, const float *out, const float *grad_loss, float *dlogits,
                             int flags, adaptseg_stream_t stream) {
   AS_CHECK_ARG(rows > 0 && c > 0 && logits && labels && out && grad_loss && dlogits, "softmax_ce_bwd: bad args");
-  int slot;  // logits + labels in, dlogits out
-  timing_begin(kTCeBwd, as_stream(stream), 8.0 * rows * c + 8.0 * rows, &slot);
-  if (c <= kRowTileMaxC)
-    ce_bwd_tiled_kernel<<<grid1d(rows, kRowTile, 8192), kRowTile, kRowTile * c * sizeof(float),
-                          as_stream(stream)>>>(rows, c, logits, labels, ignore, class_weight, out, grad_loss,
-                                               dlogits, (flags & ADAPTSEG_EPI_ACCUMULATE) ? 1 : 0);
-  else
-    ce_bwd_kernel<<<grid1d(rows), 256, 0, as_stream(stream)>>>(rows, c, logits, labels, ignore, class_weight, out,
-                                                               grad_loss, dlogits,
-                                                               (flags & ADAPTSEG_EPI_ACCUMULATE) ? 1 : 0);
-  timing_end(slot, as_stream(stream));
-  AS_CHECK_LAUNCH("ce_bwd");
-  return ADAPTSEG_OK;
+  return ce_bwd_launch(rows, c, logits, labels, ignore, class_weight, nullptr, out, grad_loss, dlogits, flags, stream);
+}
+
+int adaptseg_softmax_ce_pw_fwd(int64_t rows, int c, const float *logits, const int64_t *labels, int ignore,
+                               const float *class_weight, const float *pixel_weight, float *out, void *ws,
+                               size_t ws_bytes, adaptseg_stream_t stream) {
+  AS_CHECK_ARG(rows > 0 && c > 0, "softmax_ce_pw_fwd: bad rows %lld or c %d", (long long)rows, c);
+  AS_CHECK_ARG(logits && labels && pixel_weight && out, "softmax_ce_pw_fwd: bad args (null pointer)");
+  return ce_fwd_launch("softmax_ce_pw_fwd", rows, c, logits, labels, ignore, class_weight, pixel_weight, out, ws,
+                       ws_bytes, stream);
+}
+
+int adaptseg_softmax_ce_pw_bwd(int64_t rows, int c, const float *logits, const int64_t *labels, int ignore,
+                               const float *class_weight, const float *pixel_weight, const float *out,
+                               const float *grad_loss, float *dlogits, int flags, adaptseg_stream_t stream) {
+  AS_CHECK_ARG(rows > 0 && c > 0, "softmax_ce_pw_bwd: bad rows %lld or c %d", (long long)rows, c);
+  AS_CHECK_ARG(logits && labels && pixel_weight && out && grad_loss && dlogits,
+               "softmax_ce_pw_bwd: bad args (null pointer)");
+  return ce_bwd_launch(rows, c, logits, labels, ignore, class_weight, pixel_weight, out, grad_loss, dlogits, flags,
+                       stream);
 }
 
 // k = 1 / ln C of the entropy ops (C >= 2, checked by the callers)

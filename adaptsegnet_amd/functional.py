@@ -121,8 +121,35 @@ class _CrossEntropy2d(torch.autograd.Function):
         return K.as_nchw(dl), None, None, None, None
 
 
+class _CrossEntropy2dPW(torch.autograd.Function):
+    """_CrossEntropy2d with a weight per pixel on the numerator (no gradient to the weights)."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, ignore, weight, reduction, pixel_weight):
+        x = K.nhwc_view(logits)
+        out = K.ce_fwd(x, labels, ignore, weight, pixel_weight)   # [weighted mean, denominator]
+        ctx.save_for_backward(x, labels, out, weight, pixel_weight)
+        ctx.ignore, ctx.total = ignore, reduction == "sum"
+        if ctx.total:
+            return torch.where(out[1] > 0, out[0] * out[1], torch.zeros_like(out[0]))
+        if reduction == "mean_or_zero":
+            return torch.where(out[1] > 0, out[0], torch.zeros_like(out[0]))
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        x, labels, out, weight, pixel_weight = ctx.saved_tensors
+        if g.dim() == 0:
+            g = g.reshape(1)
+        if ctx.total:
+            g = g * out[1:2]
+        dl = K.ce_bwd(x, labels, out, g.contiguous(), ctx.ignore, weight, pixel_weight=pixel_weight)
+        return K.as_nchw(dl), None, None, None, None, None
+
+
 def cross_entropy2d(logits: torch.Tensor, labels: torch.Tensor, ignore_index: int = 255,
-                    weight: torch.Tensor | None = None, reduction: str = "mean") -> torch.Tensor:
+                    weight: torch.Tensor | None = None, reduction: str = "mean",
+                    pixel_weight: torch.Tensor | None = None) -> torch.Tensor:
     """Softmax cross entropy over pixels whose label is >= 0 and != ignore_index.
 
     logits: [N, C, H, W] fp32; labels: [N, H, W] int64.  reduction 'mean' (weighted by
@@ -130,6 +157,12 @@ def cross_entropy2d(logits: torch.Tensor, labels: torch.Tensor, ignore_index: in
     all-ignored batch gives NaN for the mean (like the reference) and 0 for the sum
     (F.cross_entropy); 'mean_or_zero' is the mean, but 0 with a zero gradient for an all-ignored
     batch (the self-training term: a batch of pseudo-labels may keep no pixel).
+
+    pixel_weight: float32 [N, H, W] or None.  Each valid pixel's term is multiplied by its weight;
+    the mean still divides by the valid pixels (their summed class weights), not by the summed
+    pixel weights: ``sum_i pw_i w_i nll_i / sum_i w_i``, so all-ones weights give the unweighted
+    loss and down-weighted pixels shrink it (the confidence weights of ``mix.classmix``).  The
+    weights get no gradient.  None runs the code path without them.
     """
     if reduction not in ("mean", "sum", "mean_or_zero"):
         raise ValueError(f"cross_entropy2d: reduction {reduction!r} (expected 'mean', 'sum' or 'mean_or_zero')")
@@ -142,6 +175,14 @@ def cross_entropy2d(logits: torch.Tensor, labels: torch.Tensor, ignore_index: in
     labels = labels.contiguous()
     if weight is not None:
         weight = weight.to(device=logits.device, dtype=torch.float32).contiguous()
+    if pixel_weight is not None:
+        if pixel_weight.dtype != torch.float32 or pixel_weight.shape != (n, h, w):
+            raise RuntimeError(f"cross_entropy2d: pixel_weight is {pixel_weight.dtype} {tuple(pixel_weight.shape)}, "
+                               f"expected float32 {(n, h, w)}")
+        if pixel_weight.device != logits.device:
+            raise RuntimeError(f"cross_entropy2d: pixel_weight is on {pixel_weight.device}, logits on {logits.device}")
+        return _CrossEntropy2dPW.apply(logits, labels, int(ignore_index), weight, reduction,
+                                       pixel_weight.detach().contiguous())
     return _CrossEntropy2d.apply(logits, labels, int(ignore_index), weight, reduction)
 
 

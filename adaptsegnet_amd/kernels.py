@@ -680,18 +680,26 @@ def softmax_bwd(y, dy, out=None, accumulate=False):
     return out
 
 
-def ce_fwd(logits, labels, ignore=255, class_weight=None):
-    """Returns a 2-element device tensor [loss, denominator]."""
+def ce_fwd(logits, labels, ignore=255, class_weight=None, pixel_weight=None):
+    """Returns a 2-element device tensor [loss, denominator].  pixel_weight (float32, one per row):
+    the pixel-weighted form, whose numerator alone carries it."""
     out = torch.empty(2, device=logits.device, dtype=torch.float32)
-    _OP.softmax_ce_fwd(logits, labels, int(ignore), class_weight, out)
+    if pixel_weight is None:
+        _OP.softmax_ce_fwd(logits, labels, int(ignore), class_weight, out)
+    else:
+        _OP.softmax_ce_pw_fwd(logits, labels, int(ignore), class_weight, pixel_weight, out)
     return out
 
 
 def ce_bwd(logits, labels, out2, grad_loss, ignore=255, class_weight=None, dl=None,
-           accumulate=False):
+           accumulate=False, pixel_weight=None):
     if dl is None:
         dl = torch.empty_like(logits)
-    _OP.softmax_ce_bwd(logits, labels, out2, grad_loss, int(ignore), class_weight, dl, bool(accumulate))
+    if pixel_weight is None:
+        _OP.softmax_ce_bwd(logits, labels, out2, grad_loss, int(ignore), class_weight, dl, bool(accumulate))
+    else:
+        _OP.softmax_ce_pw_bwd(logits, labels, out2, grad_loss, int(ignore), class_weight, pixel_weight, dl,
+                              bool(accumulate))
     return dl
 
 

@@ -31,6 +31,10 @@ Reference call sites the ops stand in for (file:line in /root/reference):
 Beyond the reference (``LOSS_NAMES``, registered like the rest but never part of an engine program):
   selfinfo_*          the weighted self-information map -p log p / ln C (ADVENT's discriminator input)
   entropy_loss_*      the entropy-minimisation loss mean(-sum_c p log p) / ln C
+and, in ``MIX_NAMES``, online self-training (DACS; adaptsegnet_amd/mix.py):
+  ema / ema_multi     the mean teacher's update over an arena / a list of small tensors
+  classmix_*          ClassMix: per-image statistics, then selection + paste in one launch
+  softmax_ce_pw_*     softmax_ce_* with a weight per pixel on the numerator
 """
 from __future__ import annotations
 
@@ -197,14 +201,15 @@ def _fake(*args, **kwargs):
 
 NAMES: list = []        # the ops the engine and the step's own kernels launch
 LOSS_NAMES: list = []   # ops of the optional loss terms around the step (engine=False): never in an engine program
+MIX_NAMES: list = []    # ops of online self-training (adaptsegnet_amd/mix.py, names=MIX_NAMES): likewise
 
 
-def _op(schema, engine=True):
+def _op(schema, engine=True, names=None):
     """Define adaptseg::<schema> with the decorated function as its CUDA kernel."""
     name = schema.split("(", 1)[0]
 
     def deco(fn):
-        (NAMES if engine else LOSS_NAMES).append(name)
+        (names if names is not None else NAMES if engine else LOSS_NAMES).append(name)
         LIB.define(schema)
         LIB.impl(name, fn, "CUDA")
         torch.library.register_fake(f"adaptseg::{name}", _fake, lib=LIB)
@@ -851,10 +856,111 @@ def _pseudo_label(pred, conf, thr, ignore_label, labels, kept):
                                            int(ignore_label), pl, pk, _stream()), "pseudo_label")
 
 
+# ---- online self-training: mean teacher, ClassMix, pixel-weighted CE (adaptsegnet_amd/mix.py) -----
+def _pt(t, dtype, shape, what):
+    """Pointer of a contiguous tensor of exactly this dtype and shape, checked on the host."""
+    if t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise RuntimeError(f"{what}: expected a contiguous {dtype} {tuple(shape)}, got {t.dtype} {tuple(t.shape)}"
+                           f"{'' if t.is_contiguous() else ' (not contiguous)'}")
+    return _p(t)
+
+
+@_op("softmax_ce_pw_fwd(Tensor logits, Tensor labels, int ignore, Tensor? weight, Tensor pixel_weight, "
+     "Tensor(a!) out) -> ()", names=MIX_NAMES)
+def _softmax_ce_pw_fwd(logits, labels, ignore, weight, pixel_weight, out):
+    """softmax_ce_fwd with pixel_weight float32 [rows] on the numerator (adaptseg_softmax_ce_pw_fwd)."""
+    rows, c = _rc(logits)
+    b = ctypes.c_size_t(0)
+    check(_lib.lib().adaptseg_ce_workspace_size(rows, ctypes.byref(b)), "ce_workspace_size")
+    wp, wsz = _ws_args(b.value, logits.device)
+    check(_lib.lib().adaptseg_softmax_ce_pw_fwd(
+        rows, c, _pf(logits, rows * c, "softmax_ce_pw_fwd logits"), _p(labels), int(ignore), _p(weight),
+        _pf(pixel_weight, rows, "softmax_ce_pw_fwd pixel_weight"), _pf(out, 2, "softmax_ce_pw_fwd out"), wp, wsz,
+        _stream()), "softmax_ce_pw_fwd")
+
+
+@_op("softmax_ce_pw_bwd(Tensor logits, Tensor labels, Tensor out, Tensor grad_loss, int ignore, Tensor? weight, "
+     "Tensor pixel_weight, Tensor(a!) dlogits, bool accumulate) -> ()", names=MIX_NAMES)
+def _softmax_ce_pw_bwd(logits, labels, out, grad_loss, ignore, weight, pixel_weight, dlogits, accumulate):
+    rows, c = _rc(logits)
+    check(_lib.lib().adaptseg_softmax_ce_pw_bwd(
+        rows, c, _pf(logits, rows * c, "softmax_ce_pw_bwd logits"), _p(labels), int(ignore), _p(weight),
+        _pf(pixel_weight, rows, "softmax_ce_pw_bwd pixel_weight"), _pf(out, 2, "softmax_ce_pw_bwd out"),
+        _pf(grad_loss, 1, "softmax_ce_pw_bwd grad_loss"), _pf(dlogits, rows * c, "softmax_ce_pw_bwd dlogits"),
+        _lib.EPI_ACCUMULATE if accumulate else 0, _stream()), "softmax_ce_pw_bwd")
+
+
+@_op("ema(Tensor src, Tensor(a!) dst, float alpha) -> ()", names=MIX_NAMES)
+def _ema(src, dst, alpha):
+    """dst = fmaf(alpha, dst, (1 - alpha) * src) over two contiguous float32 tensors of one size (adaptseg_ema)."""
+    n = dst.numel()
+    if not (src.is_contiguous() and dst.is_contiguous()):
+        raise RuntimeError("ema: src and dst must be contiguous")
+    check(_lib.lib().adaptseg_ema(n, float(alpha), _pf(src, n, "ema src"), _pf(dst, n, "ema dst"), _stream()), "ema")
+
+
+@_op("ema_multi(Tensor[] src, Tensor(a!)[] dst, float alpha) -> ()", names=MIX_NAMES)
+def _ema_multi(src, dst, alpha):
+    """ema over a list of (small) tensor pairs in ceil(len / _lib.EMA_CHUNK) launches (adaptseg_ema_multi)."""
+    if len(src) != len(dst):
+        raise RuntimeError(f"ema_multi: {len(src)} sources for {len(dst)} destinations")
+    m = len(dst)
+    ps, pd, pn = (ctypes.c_void_p * m)(), (ctypes.c_void_p * m)(), (ctypes.c_int64 * m)()
+    for i, (s, d) in enumerate(zip(src, dst)):
+        if not (s.is_contiguous() and d.is_contiguous()):
+            raise RuntimeError(f"ema_multi: tensor {i} is not contiguous")
+        n = d.numel()
+        ps[i], pd[i], pn[i] = _pf(s, n, f"ema_multi src {i}").value, _pf(d, n, f"ema_multi dst {i}").value, n
+    check(_lib.lib().adaptseg_ema_multi(m, ps, pd, pn, float(alpha), _stream()), "ema_multi")
+
+
+@_op("classmix_stats(Tensor labels_s, Tensor conf_t, float tau, int num_classes, Tensor(a!) count, "
+     "Tensor(b!) nconf) -> ()", names=MIX_NAMES)
+def _classmix_stats(labels_s, conf_t, tau, num_classes, count, nconf):
+    """count int32 [N, C] = source pixels per class, nconf int32 [N] = target pixels with conf >= tau."""
+    if labels_s.dim() != 3:
+        raise RuntimeError(f"classmix_stats: labels_s is {tuple(labels_s.shape)}, expected [N, H, W]")
+    n, h, w = labels_s.shape
+    c = int(num_classes)
+    check(_lib.lib().adaptseg_classmix_stats(
+        n, h, w, c, _pt(labels_s, torch.int64, (n, h, w), "classmix_stats labels_s"),
+        _pt(conf_t, torch.float32, (n, h, w), "classmix_stats conf_t"), float(tau),
+        _pt(count, torch.int32, (n, c), "classmix_stats count"), _pt(nconf, torch.int32, (n,), "classmix_stats nconf"),
+        _stream()), "classmix_stats")
+
+
+@_op("classmix_apply(Tensor images_s, Tensor labels_s, Tensor images_t, Tensor pred_t, Tensor count, Tensor nconf, "
+     "Tensor keys, int ignore_label, Tensor(a!) mixed_images, Tensor(b!) mixed_labels, Tensor(c!) mixed_weights, "
+     "Tensor(d!)? mask) -> ()", names=MIX_NAMES)
+def _classmix_apply(images_s, labels_s, images_t, pred_t, count, nconf, keys, ignore_label, mixed_images, mixed_labels,
+                    mixed_weights, mask):
+    """keys: the uint32 [N, C] random numbers, held in an int32 tensor (torch has no arithmetic on uint32)."""
+    if images_s.dim() != 4 or images_s.shape[1] != 3:
+        raise RuntimeError(f"classmix_apply: images_s is {tuple(images_s.shape)}, expected [N, 3, H, W]")
+    n, _, h, w = images_s.shape
+    if count.dim() != 2:
+        raise RuntimeError(f"classmix_apply: count is {tuple(count.shape)}, expected [N, C]")
+    c = count.shape[1]
+    if tuple(images_t.shape) != (n, 3, h, w):
+        raise RuntimeError(f"classmix_apply: target images {tuple(images_t.shape)} vs source images "
+                           f"{tuple(images_s.shape)}: ClassMix pastes pixel on pixel, the sizes must agree")
+    what = "classmix_apply"
+    check(_lib.lib().adaptseg_classmix_apply(
+        n, h, w, c, _pt(images_s, torch.float32, (n, 3, h, w), f"{what} images_s"),
+        _pt(labels_s, torch.int64, (n, h, w), f"{what} labels_s"),
+        _pt(images_t, torch.float32, (n, 3, h, w), f"{what} images_t"),
+        _pt(pred_t, torch.uint8, (n, h, w), f"{what} pred_t"), _pt(count, torch.int32, (n, c), f"{what} count"),
+        _pt(nconf, torch.int32, (n,), f"{what} nconf"), _pt(keys, torch.int32, (n, c), f"{what} keys"),
+        int(ignore_label), _pt(mixed_images, torch.float32, (n, 3, h, w), f"{what} mixed_images"),
+        _pt(mixed_labels, torch.int64, (n, h, w), f"{what} mixed_labels"),
+        _pt(mixed_weights, torch.float32, (n, h, w), f"{what} mixed_weights"),
+        None if mask is None else _pt(mask, torch.uint8, (n, c), f"{what} mask"), _stream()), what)
+
+
 class _Overloads:
     """torch.ops.adaptseg.<name>.default for every op (skips the packet's overload lookup)."""
 
 
 OPS = _Overloads()
-for _n in NAMES + LOSS_NAMES:
+for _n in NAMES + LOSS_NAMES + MIX_NAMES:
     setattr(OPS, _n, getattr(torch.ops.adaptseg, _n).default)

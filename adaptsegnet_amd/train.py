@@ -29,6 +29,8 @@ element (adaptsegnet_amd/pseudo.py; the CBST / BDL stage after adaptation).  At 
 the step is the reference's.  ``StepConfig.d_input="entropy"`` and ``StepConfig.lambda_ent > 0`` are the
 two halves of entropy-based adaptation (ADVENT): the discriminators see the weighted self-information
 map of a prediction instead of its softmax, and the target branch adds an entropy-minimisation loss.
+``StepConfig.lambda_mix > 0`` is online self-training (DACS; adaptsegnet_amd/mix.py): a third generator
+forward on a ClassMix image made by a mean teacher, trained with a confidence-weighted cross entropy.
 
 Data parallel (one process per GPU): every rank runs the step on its own shard, and SUM
 all-reduces of the gradient arenas replace DataParallel's gradient gather
@@ -87,6 +89,17 @@ class StepConfig:
     # weighting of head 1); batches keep their shape.  The defaults are the step as it was
     d_input: str = "softmax"
     lambda_ent: float = 0.0
+    # online self-training (DACS: mean teacher + ClassMix, adaptsegnet_amd/mix.py).  With
+    # lambda_mix > 0 every batch ends with three more elements, after the optional labels_target:
+    # (mixed_images float32 [N, 3, H, W], mixed_labels int64 [N, H, W], mixed_weights float32
+    # [N, H, W]) at ``input_size`` (``EmaTeacher.mix``), and the sub-iteration gains a third generator
+    # forward, on mixed_images, whose backward is lambda_mix * cross_entropy2d(pred2, mixed_labels,
+    # reduction="mean_or_zero", pixel_weight=mixed_weights) (multi-level: + lambda_seg * lambda_mix *
+    # the same on pred1).  It runs on the main stream after the target branch's backward and is then
+    # the sub-iteration's last generator backward.  Allowed at every level: "source-only" with it
+    # is plain DACS, its batches (images, labels, mixed_images, mixed_labels, mixed_weights).
+    # 0: the step as it was
+    lambda_mix: float = 0.0
     # run the target-domain generator forward (+ its D forward) on a second HIP stream while
     # the source-domain backward executes (independent: same weights, read-only, separate
     # gradient kernels); the target backward then waits for the source backward.  Results are
@@ -159,6 +172,11 @@ class AdaptSegTrainer:
         if cfg.lambda_ent > 0 and cfg.level == "source-only":
             raise ValueError("lambda_ent > 0: the entropy term belongs to the target branch of the "
                              "single-level / multi-level steps; the source-only step has none")
+        if cfg.lambda_mix < 0:
+            raise ValueError(f"lambda_mix {cfg.lambda_mix!r} (expected >= 0)")
+        if cfg.lambda_mix > 0 and warper is not None:
+            raise ValueError("lambda_mix > 0 with a warper: the mixed image has no flow field of its own "
+                             "(the warper's field belongs to the source image)")
         if cfg.level != "source-only" and model_D2 is None:
             raise ValueError(f"{cfg.level} needs model_D2")
         if warper is not None and (cfg.level == "multi-level" or getattr(model, "single_output", False)):
@@ -383,7 +401,8 @@ class AdaptSegTrainer:
 
     def _step_body(self, i_iter, batches):
         """batches: iterable of ``iter_size`` tuples (images, labels, images_target), or with
-        ``cfg.lambda_st > 0`` (images, labels, images_target, labels_target).
+        ``cfg.lambda_st > 0`` (images, labels, images_target, labels_target); with
+        ``cfg.lambda_mix > 0`` each ends with (mixed_images, mixed_labels, mixed_weights) besides.
 
         Multi-GPU: the generator's gradients are final after its adversarial backward of the
         last sub-iteration, so their all-reduce (the 178 MB arena) is launched right there and
@@ -392,9 +411,13 @@ class AdaptSegTrainer:
         c = self.cfg
         batches = list(batches)
         tsize = self._target_size()
+        nmix = 3 if c.lambda_mix > 0 else 0
         if c.lambda_st > 0:   # a malformed self-training batch raises before anything is launched
             for batch in batches:
-                self._st_labels(batch, tsize)
+                self._st_labels(batch, tsize, nmix)
+        if nmix:              # and so does a malformed mixed triple
+            for batch in batches:
+                self._mix_elements(batch)
         L = StepLosses()
         self.opt.zero_grad()
         for o in (self.opt_D1, self.opt_D2):
@@ -405,15 +428,16 @@ class AdaptSegTrainer:
         self._pending = []
         for idx, batch in enumerate(batches):
             g_done = _GSync(self) if idx == len(batches) - 1 else None
+            mixed = tuple(batch[-3:]) if nmix else None
             if c.level == "source-only":
-                self._sub_source_only(batch[0], batch[1], inv, L, g_done)
+                self._sub_source_only(batch[0], batch[1], inv, L, g_done, mixed)
                 continue
             images, labels, images_t = batch[:3]
             labels_t = batch[3] if c.lambda_st > 0 else None
             if c.level == "single-level":
-                self._sub_single(images, labels, images_t, inv, tsize, L, g_done, labels_t)
+                self._sub_single(images, labels, images_t, inv, tsize, L, g_done, labels_t, mixed)
             else:
-                self._sub_multi(images, labels, images_t, inv, tsize, L, g_done, labels_t)
+                self._sub_multi(images, labels, images_t, inv, tsize, L, g_done, labels_t, mixed)
         if not batches:
             self._start_sync((self.model,))
         if batches and c.level != "source-only":
@@ -428,10 +452,12 @@ class AdaptSegTrainer:
         return L
 
     @staticmethod
-    def _st_labels(batch, tsize):
-        """The fourth element of a self-training batch, checked against the target prediction's size."""
-        if len(batch) != 4:
-            raise ValueError(f"lambda_st > 0: every batch is (images, labels, images_target, labels_target); "
+    def _st_labels(batch, tsize, nmix=0):
+        """The fourth element of a self-training batch, checked against the target prediction's size
+        (``nmix``: the elements that follow it, the mixed triple of lambda_mix > 0)."""
+        if len(batch) != 4 + nmix:
+            raise ValueError(f"lambda_st > 0: every batch is (images, labels, images_target, labels_target"
+                             f"{', mixed_images, mixed_labels, mixed_weights' if nmix else ''}); "
                              f"got {len(batch)} elements")
         images_t, labels_t = batch[2], batch[3]
         want = (images_t.shape[0], int(tsize[1]), int(tsize[0]))
@@ -439,6 +465,47 @@ class AdaptSegTrainer:
             raise ValueError(f"labels_target is {labels_t.dtype} {tuple(labels_t.shape)}: expected int64 {want}, "
                              f"[N, H, W] at the size the target prediction is upsampled to (W, H) = {tuple(tsize)}")
         return labels_t
+
+    def _mix_elements(self, batch):
+        """The last three elements of a lambda_mix > 0 batch, checked against ``input_size``."""
+        c = self.cfg
+        base = (2 if c.level == "source-only" else 3) + (1 if c.lambda_st > 0 else 0)
+        if len(batch) != base + 3:
+            raise ValueError(f"lambda_mix > 0: every batch ends with (mixed_images, mixed_labels, mixed_weights) "
+                             f"after its {base} other elements; got {len(batch)} elements")
+        images, (mi, ml, mw) = batch[0], batch[-3:]
+        n, (w, h) = images.shape[0], (int(c.input_size[0]), int(c.input_size[1]))
+        for name, t, dtype, want in (("mixed_images", mi, torch.float32, (n, 3, h, w)),
+                                     ("mixed_labels", ml, torch.int64, (n, h, w)),
+                                     ("mixed_weights", mw, torch.float32, (n, h, w))):
+            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != want:
+                got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+                raise ValueError(f"{name} is {got}: expected {dtype} {want}, at input_size (W, H) = "
+                                 f"{tuple(c.input_size)}")
+        return mi, ml, mw
+
+    def _sub_mixed(self, mixed, inv, L, g_done):
+        """The mixed branch (lambda_mix > 0): a third generator forward, on the ClassMix image, and the
+        confidence-weighted CE against the mixed labels.  On the main stream, after the target
+        branch's backward and the side stream's join (its BatchNorm running-statistics updates
+        must not race the overlapped target forward); the sub-iteration's last generator backward,
+        so ``g_done`` wraps it.  The discriminator step does not depend on it."""
+        c = self.cfg
+        mi, ml, mw = mixed
+        if c.level == "multi-level":
+            pred1, pred2 = self.model(mi, c.input_size)
+            preds, scales, names = [pred2, pred1], [c.lambda_mix * inv, c.lambda_seg * c.lambda_mix * inv], \
+                ["loss_mix2", "loss_mix1"]
+        else:
+            preds, scales, names = [self._pred_single(mi, c.input_size)], [c.lambda_mix * inv], ["loss_mix2"]
+        losses = [F.cross_entropy2d(p, ml, c.ignore_label, reduction="mean_or_zero", pixel_weight=mw) for p in preds]
+        if g_done is not None:
+            g_done.begin()
+        self._backward(losses, scales)
+        for name, t in zip(names, losses):
+            L.add(name, t, inv)
+        if g_done is not None:
+            g_done.end()
 
     def _st_loss(self, pred_target, labels_t, ov):
         """CE of a target prediction against the pseudo-labels, on the stream the target branch runs
@@ -462,19 +529,22 @@ class AdaptSegTrainer:
     def _flow(self, images):
         return None if self.warper is None else self.warper(images)[0]
 
-    def _sub_source_only(self, images, labels, inv, L, g_done=None):
+    def _sub_source_only(self, images, labels, inv, L, g_done=None, mixed=None):
         """train_gta2cityscapes_multi.py:259-286: warper (if any), segmentation loss on the
         second head, backward; the step is the generator's SGD only."""
         pred2 = self._pred_single(images, self.cfg.input_size, self._flow(images))
         loss_seg2 = F.cross_entropy2d(pred2, labels, self.cfg.ignore_label)
-        if g_done is not None:
-            g_done.begin()
+        last = g_done if mixed is None else None   # with a mixed branch, that is the last generator backward
+        if last is not None:
+            last.begin()
         self._backward([loss_seg2], [inv])
         L.add("loss_seg2", loss_seg2, inv)
-        if g_done is not None:
-            g_done.end()
+        if last is not None:
+            last.end()
+        if mixed is not None:
+            self._sub_mixed(mixed, inv, L, g_done)
 
-    def _sub_single(self, images, labels, images_t, inv, tsize, L, g_done=None, labels_t=None):
+    def _sub_single(self, images, labels, images_t, inv, tsize, L, g_done=None, labels_t=None, mixed=None):
         """train_gta2cityscapes_multi.py:385-461."""
         c, D2 = self.cfg, self.D2
         self._set_requires_grad(D2, False)
@@ -503,8 +573,9 @@ class AdaptSegTrainer:
             dev_ = loss_adv_target2.device
             dfork = self._d_fork(dev_)
             self._join_source(ov)
-            if g_done is not None:
-                g_done.begin()
+            last = g_done if mixed is None else None   # with a mixed branch, that is the last generator backward
+            if last is not None:
+                last.begin()
             self._backward([loss_adv_target2] + loss_st + loss_ent,
                            [c.lambda_adv_target2 * inv] + [c.lambda_st * inv] * len(loss_st)
                            + [c.lambda_ent * inv] * len(loss_ent))
@@ -513,9 +584,11 @@ class AdaptSegTrainer:
                 L.add("loss_st2", t, inv)
             for t in loss_ent:
                 L.add("loss_ent2", t, inv)
-            if g_done is not None:
-                g_done.end()
+            if last is not None:
+                last.end()
         self._overlap_end(ov, pred_target2, loss_adv_target2, *loss_st, *loss_ent, *self._kept(keep2))
+        if mixed is not None:
+            self._sub_mixed(mixed, inv, L, g_done)
 
         self._set_requires_grad(D2, True)
         pred2 = pred2.detach()
@@ -528,7 +601,7 @@ class AdaptSegTrainer:
             self._backward([loss_d2], [inv / 2])
             L.add("loss_D2", loss_d2, inv / 2)
 
-    def _sub_multi(self, images, labels, images_t, inv, tsize, L, g_done=None, labels_t=None):
+    def _sub_multi(self, images, labels, images_t, inv, tsize, L, g_done=None, labels_t=None, mixed=None):
         """train_gta2cityscapes_multi.py:578-679."""
         c, D1, D2 = self.cfg, self.D1, self.D2
         self._set_requires_grad(D1, False)
@@ -560,8 +633,9 @@ class AdaptSegTrainer:
             dev_ = loss_adv2.device
             dfork = self._d_fork(dev_)
             self._join_source(ov)
-            if g_done is not None:
-                g_done.begin()
+            last = g_done if mixed is None else None   # with a mixed branch, that is the last generator backward
+            if last is not None:
+                last.begin()
             st_scales = [c.lambda_seg * c.lambda_st * inv, c.lambda_st * inv][:len(loss_st)]
             ent_scales = [c.lambda_seg * c.lambda_ent * inv, c.lambda_ent * inv][:len(loss_ent)]
             self._backward([loss_adv1, loss_adv2] + loss_st + loss_ent,
@@ -572,10 +646,12 @@ class AdaptSegTrainer:
                 L.add(name, t, inv)
             for name, t in zip(("loss_ent1", "loss_ent2"), loss_ent):
                 L.add(name, t, inv)
-            if g_done is not None:
-                g_done.end()
+            if last is not None:
+                last.end()
         self._overlap_end(ov, pred_target1, pred_target2, loss_adv1, loss_adv2, *loss_st, *loss_ent,
                           *self._kept(keep1, keep2))
+        if mixed is not None:
+            self._sub_mixed(mixed, inv, L, g_done)
 
         self._set_requires_grad(D1, True)
         self._set_requires_grad(D2, True)

@@ -491,6 +491,53 @@ int adaptseg_pseudo_label(int64_t npix, const uint8_t *pred, const float *conf, 
                           adaptseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------ */
+/* Online self-training (the DACS recipe): a mean teacher and ClassMix.  Stands in for no    */
+/* reference call.  Integer atomics only, no host sync, the caller's stream.                */
+/* ------------------------------------------------------------------------------------ */
+/* dst[i] = fmaf(alpha, dst[i], (1 - alpha) * src[i]) for i < n, with 1 - alpha rounded once to
+   fp32 on the host: two roundings per element, whatever the contraction flags.  The end points
+   are exact copies of bits: alpha == 0 stores src[i] (also over a non-finite dst, and keeping
+   the sign of a zero), alpha == 1 launches nothing.  One launch for any n (a parameter arena):
+   a grid of at most ADAPTSEG_EMA_MAX_BLOCKS blocks of 256 threads x 4 elements sweeps it, with
+   16-byte accesses when both pointers are 16-byte aligned and a scalar tail.  Rejected on the
+   host (ADAPTSEG_ERR_ARG): n < 0, alpha outside [0, 1] or NaN, a NULL pointer with n > 0. */
+#define ADAPTSEG_EMA_MAX_BLOCKS 2048
+int adaptseg_ema(int64_t n, float alpha, const float *src, float *dst, adaptseg_stream_t stream);
+/* The same rule over `count` small tensors (BatchNorm statistics): src / dst / n are HOST tables
+   of device pointers and lengths, passed to the kernel by value ADAPTSEG_EMA_CHUNK tensors per
+   launch.  Also rejected: count < 0, a NULL table, a length outside [0, 2^31). */
+#define ADAPTSEG_EMA_CHUNK 128
+int adaptseg_ema_multi(int count, const float *const *src, float *const *dst, const int64_t *n, float alpha,
+                       adaptseg_stream_t stream);
+/* ClassMix, pass 1.  labels_s int64 [n][h][w] (source labels), conf_t fp32 [n][h][w] (the
+   teacher's confidence on the target images):
+     count[i][c] = #pixels of source image i with label c, 0 <= c < ncls   (int32 [n][ncls])
+     nconf[i]    = #pixels of target image i with conf >= tau (a NaN does not count) (int32 [n])
+   Both are overwritten (cleared on the stream first).  Block-private LDS counts, then integer
+   adds: exact and order-independent. */
+int adaptseg_classmix_stats(int n, int h, int w, int ncls, const int64_t *labels_s, const float *conf_t,
+                            float tau, int32_t *count, int32_t *nconf, adaptseg_stream_t stream);
+/* ClassMix, pass 2.  Per image i, from count[i][:] and keys[i][:] (uint32 [n][ncls], the caller's
+   random numbers): the classes present are those with count > 0, k of them; the ceil(k / 2)
+   present classes with the smallest (key, class index) pairs are SELECTED (k == 0: none).  Every
+   block recomputes its image's selection, so no value returns to the host.  Per pixel p, with
+   m = (0 <= labels_s[p] < ncls and labels_s[p] is selected):
+     mixed_images[:, p] = m ? images_s[:, p] : images_t[:, p]     (fp32 [n][3][h][w], contiguous)
+     mixed_labels[p]    = m ? labels_s[p] : (pred_t[p] < ncls ? pred_t[p] : ignore_label)  (int64)
+     mixed_weights[p]   = m ? 1.0f : q_i,  q_i = (float)nconf[i] / (float)(h * w)  (one fp32 division)
+   mask (uint8 [n][ncls], may be NULL) = the selection.  pred_t is the teacher's uint8 class map.
+   16-byte accesses when h * w % 4 == 0 and every pointer is 16-byte aligned, scalar ones
+   otherwise.  No output may alias an input.  Rejected on the host (ADAPTSEG_ERR_ARG), here and
+   in pass 1: ncls outside 1..256, n, h or w < 1, h * w >= 2^24 (q_i's operands are then exact
+   in fp32), ignore_label outside 0..255, a NULL pointer. */
+#define ADAPTSEG_CLASSMIX_MAX_BLOCKS 512 /* blocks per image, each sweep 256 threads x 4 pixels */
+int adaptseg_classmix_apply(int n, int h, int w, int ncls, const float *images_s, const int64_t *labels_s,
+                            const float *images_t, const uint8_t *pred_t, const int32_t *count,
+                            const int32_t *nconf, const uint32_t *keys, int ignore_label, float *mixed_images,
+                            int64_t *mixed_labels, float *mixed_weights, uint8_t *mask,
+                            adaptseg_stream_t stream);
+
+/* ------------------------------------------------------------------------------------ */
 /* Input pipeline: GTA5DataSet.__getitem__ after file decode (dataset/gta5_dataset.py:47-71) */
 /* and the target loader's image path (train_gta2cityscapes_multi.py:333-336, 520-523).    */
 /* Bit-exact with Pillow's Image.resize(crop, BICUBIC) / (crop, NEAREST) 8-bit resampler.   */
@@ -574,6 +621,19 @@ int adaptseg_softmax_ce_bwd(int64_t rows, int c, const float *logits, const int6
                             int ignore, const float *class_weight, const float *out,
                             const float *grad_loss, float *dlogits, int flags,
                             adaptseg_stream_t stream);
+/* The same with a weight per pixel (pixel_weight fp32 [rows], not NULL; the confidence weights
+   of adaptseg_classmix_apply):
+     out[0] = sum_i pw_i cw_i nll_i / sum_i cw_i,  out[1] = sum_i cw_i   over the valid rows
+   (the denominator does not hold pw: with pw == 1 everywhere these are the plain forms, bit for
+   bit), and dlogits = grad_loss[0] / out[1] * pw_i * cw_i * (softmax - onehot).  Same workspace,
+   same two kernel families (LDS tiles for c <= 32, one thread per row above), same flags. */
+int adaptseg_softmax_ce_pw_fwd(int64_t rows, int c, const float *logits, const int64_t *labels,
+                               int ignore, const float *class_weight, const float *pixel_weight,
+                               float *out, void *ws, size_t ws_bytes, adaptseg_stream_t stream);
+int adaptseg_softmax_ce_pw_bwd(int64_t rows, int c, const float *logits, const int64_t *labels,
+                               int ignore, const float *class_weight, const float *pixel_weight,
+                               const float *out, const float *grad_loss, float *dlogits, int flags,
+                               adaptseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Entropy-based adaptation (ADVENT; stands in for no reference call).  x [rows][c] logits, */
