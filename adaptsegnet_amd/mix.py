@@ -19,8 +19,13 @@ returns to the host between the teacher's forward and the step:
   ``mixed_weight = m ? 1 : q``, where m = "the source pixel's label is a selected class" and
   ``q = nconf / (H * W)`` in fp32.
 * ``functional.cross_entropy2d(..., pixel_weight=mixed_weights)`` is the loss.
+* ``strong_augment`` / ``EmaTeacher.mix(..., augment=StrongAugSampler())``: DACS's colour jitter (brightness,
+  contrast, saturation, hue in a random order) and Gaussian blur of the mixed images, each per image and
+  optional, in one launch for the batch (csrc/strongaug.hip).  The host draws the parameters and the
+  blur's half kernel; the device runs fp32 ``+ - * / floor``, compares and selects only.
 
-tests/classmix_ref.py restates the rules in numpy; tests/test_classmix_gpu.py compares bit for bit.
+tests/classmix_ref.py and tests/strongaug_ref.py restate the rules in numpy; tests/test_classmix_gpu.py and
+tests/test_strongaug_gpu.py compare bit for bit.
 
 Deliberate differences from DACS:
 
@@ -28,13 +33,20 @@ Deliberate differences from DACS:
   how a batch is sharded over ranks.  At batch 1 the two coincide.
 * The loss's mean divides by the number of valid pixels, not by all pixels (``cross_entropy2d``'s
   ``mean_or_zero``, like every other CE term of the step).
-* DACS's colour jitter and Gaussian blur of the mixed image are out of scope.
+* The jitter's and the blur's parameters are drawn per image, not per batch, for the same reason as ``q``.
+* The blur has one radius, ``min(ceil(6 sigma), (ceil(0.1 min(H, W)) - 1) // 2)``: DACS's kernel-size rule
+  applied to the shorter side where DACS sizes each axis on its own (the two coincide once both sides are
+  >= 141), and trimmed to the taps that matter in fp32 (the mass beyond 6 sigma is below 2^-24 of the sum).
 """
 from __future__ import annotations
+
+import math
 
 import numpy as np
 import torch
 
+from ._lib import BLUR_MAX_RADIUS
+from .data import IMG_MEAN
 from .evaluate import predict_tta
 from .ops import OPS
 
@@ -131,6 +143,139 @@ class ClassMixSampler:
 
     def set_state(self, state: dict) -> None:
         self.rng.bit_generator.state = state
+
+
+def blur_radius(sigma: float, h: int, w: int) -> int:
+    """``min(ceil(6 sigma), (ceil(0.1 min(h, w)) - 1) // 2)``: the taps that matter in fp32, under DACS's
+    kernel-size rule on the shorter side (0.1 of it, made odd downwards)."""
+    side = min(int(h), int(w))
+    return max(0, min(math.ceil(6.0 * float(sigma)), (math.ceil(0.1 * side) - 1) // 2))
+
+
+def blur_weights(sigma: float, radius: int) -> np.ndarray:
+    """The half kernel w[0..7] (float32, zero beyond ``radius``) of a Gaussian over d = -R..R: ``exp(-d^2 / 2
+    sigma^2)`` normalised in fp64, then rounded.  w[d] serves both d and -d: symmetric by construction."""
+    d = np.arange(0, int(radius) + 1, dtype=np.float64)
+    g = np.exp(-(d * d) / (2.0 * float(sigma) * float(sigma)))
+    total = g[0] + 2.0 * g[1:].sum()
+    out = np.zeros(BLUR_MAX_RADIUS + 1, dtype=np.float32)
+    out[:int(radius) + 1] = (g / total).astype(np.float32)
+    return out
+
+
+AUG_OPS = ("brightness", "contrast", "saturation", "hue")   # the op codes 0..3 of ``params["order"]``
+_PERMS = None
+
+
+def _perms():
+    global _PERMS
+    if _PERMS is None:
+        import itertools
+        _PERMS = np.array(list(itertools.permutations(range(4))), dtype=np.uint8)
+    return _PERMS
+
+
+class StrongAugSampler:
+    """Draws ``strong_augment``'s per-image parameters on the host.
+
+    numpy's PCG64 seeded from (seed, rank), like ``ClassMixSampler``; ``get_state`` / ``set_state`` let a
+    resumed run continue the sequence.  Every image takes eight variates whatever they decide (two
+    on/off draws, four jitter factors, the order, sigma), so the stream's position after ``sample``
+    depends on ``n`` alone."""
+
+    def __init__(self, seed=1234, rank=0, strength=0.2, p_jitter=0.8, p_blur=0.5, sigma=(0.15, 1.15)):
+        if not 0.0 <= float(strength) < 1.0:
+            raise ValueError(f"StrongAugSampler: strength {strength!r} (expected 0 <= strength < 1)")
+        for name, p in (("p_jitter", p_jitter), ("p_blur", p_blur)):
+            if not 0.0 <= float(p) <= 1.0:
+                raise ValueError(f"StrongAugSampler: {name} {p!r} (expected 0 <= p <= 1)")
+        lo, hi = float(sigma[0]), float(sigma[1])
+        if not 0.0 < lo <= hi:
+            raise ValueError(f"StrongAugSampler: sigma {sigma!r} (expected 0 < low <= high)")
+        self.strength, self.p_jitter, self.p_blur, self.sigma = float(strength), float(p_jitter), float(p_blur), (lo, hi)
+        self.rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(seed), int(rank)])))
+
+    def sample(self, n: int, h: int, w: int) -> dict:
+        """The parameters of ``n`` images of ``h`` x ``w`` pixels: ``jitter`` bool [n]; ``db``, ``fc``, ``fs``,
+        ``fh`` float32 [n] (``db``, ``fc - 1``, ``fs - 1`` and ``fh`` uniform in [-strength, strength]);
+        ``order`` uint8 [n, 4], a permutation of the op codes (``AUG_OPS``); ``sigma`` float64 [n]; ``radius``
+        int32 [n] (0: no blur); ``weights`` float32 [n, 8], the half kernels (``blur_weights``)."""
+        n = int(n)
+        u = self.rng.random((n, 8))   # a fixed number of variates per image
+        s = self.strength
+        jit = (2.0 * u[:, 2:6] - 1.0) * s
+        sigma = self.sigma[0] + u[:, 7] * (self.sigma[1] - self.sigma[0])
+        blur = u[:, 1] < self.p_blur
+        radius = np.array([blur_radius(sg, h, w) if on else 0 for sg, on in zip(sigma, blur)], dtype=np.int32)
+        radius = np.minimum(radius, BLUR_MAX_RADIUS).astype(np.int32)
+        weights = np.stack([blur_weights(sg, r) for sg, r in zip(sigma, radius)]) if n else np.zeros((0, 8), np.float32)
+        order = _perms()[np.minimum((u[:, 6] * 24).astype(np.int64), 23)]
+        return {"jitter": u[:, 0] < self.p_jitter,
+                "db": jit[:, 0].astype(np.float32), "fc": (1.0 + jit[:, 1]).astype(np.float32),
+                "fs": (1.0 + jit[:, 2]).astype(np.float32), "fh": jit[:, 3].astype(np.float32),
+                "order": order, "sigma": sigma, "radius": radius, "weights": weights}
+
+    def get_state(self) -> dict:
+        return self.rng.bit_generator.state
+
+    def set_state(self, state: dict) -> None:
+        self.rng.bit_generator.state = state
+
+
+def _aug_tables(params, n, h, w):
+    """(host controls, 4 ints per image; the [16 n] float32 table ``OPS.strong_augment`` uploads), after checking
+    everything the kernel indexes or branches with: what is wrong raises here, before any launch."""
+    def col(key, dtype, shape):
+        a = np.asarray(params[key])
+        if a.shape != shape:
+            raise ValueError(f"strong_augment: params[{key!r}] is {a.shape}, expected {shape}")
+        return a.astype(dtype)
+    on = col("jitter", np.int32, (n,)) != 0
+    radius = col("radius", np.int64, (n,))
+    order = col("order", np.int64, (n, 4))
+    fac = np.stack([col(k, np.float32, (n,)) for k in ("db", "fc", "fs", "fh")], axis=1)
+    weights = col("weights", np.float32, (n, BLUR_MAX_RADIUS + 1))
+    cap = min(BLUR_MAX_RADIUS, min(h, w) - 1)
+    if ((radius < 0) | (radius > cap)).any():
+        raise ValueError(f"strong_augment: radius {radius.tolist()} on {h} x {w} images (expected 0 <= R <= "
+                         f"min({BLUR_MAX_RADIUS}, min(H, W) - 1) = {cap})")
+    if not (np.sort(order, axis=1) == np.arange(4)).all():
+        raise ValueError(f"strong_augment: order {order.tolist()}: every row must be a permutation of 0..3")
+    if not (np.isfinite(fac).all() and np.isfinite(weights).all()):
+        raise ValueError("strong_augment: a jitter factor or a blur weight is not finite")
+    if (weights * (np.arange(BLUR_MAX_RADIUS + 1) > radius[:, None])).any():
+        raise ValueError("strong_augment: a blur weight beyond its image's radius is not zero")
+    ctl = np.zeros((n, 4), dtype=np.int32)
+    ctl[:, 0] = on
+    ctl[:, 1] = (order << (2 * np.arange(4))).sum(axis=1)
+    ctl[:, 2] = radius
+    table = np.concatenate([ctl.view(np.float32).ravel(), fac.ravel(), weights.ravel()])
+    return ctl.ravel().tolist(), table
+
+
+def strong_augment(images: torch.Tensor, params: dict, mean=IMG_MEAN) -> torch.Tensor:
+    """DACS's colour jitter, then Gaussian blur, per image of a float32 [N, 3, H, W] batch (BGR minus ``mean``, what
+    ``classmix`` returns), in one launch.  ``params``: ``StrongAugSampler.sample(N, H, W)`` (or a dictionary of
+    that form).  An image with its jitter off and radius 0 is copied bit for bit.  Any memory layout is accepted;
+    the result is a new contiguous tensor.  The tables reach the device through pinned staging: no sync."""
+    if images.dim() != 4 or images.shape[1] != 3 or images.dtype != torch.float32:
+        raise RuntimeError(f"strong_augment: images is {images.dtype} {tuple(images.shape)}, expected float32 "
+                           "[N, 3, H, W]")
+    n, _, h, w = images.shape
+    if n < 1 or h < 1 or w < 1 or h * w >= 1 << 24:
+        raise ValueError(f"strong_augment: {n} images of {h} x {w} pixels (expected N, H, W >= 1, H * W < 2^24)")
+    mean = [float(v) for v in np.asarray(mean, dtype=np.float32).reshape(-1)]
+    if len(mean) != 3 or not all(math.isfinite(v) for v in mean):
+        raise ValueError(f"strong_augment: mean {mean!r} (expected three finite floats, B G R)")
+    ctl, table = _aug_tables(params, n, h, w)
+    t = torch.from_numpy(table)
+    if images.device.type == "cuda":
+        t = t.pin_memory()
+    t = t.to(images.device, non_blocking=True)
+    images = images.contiguous()
+    out = torch.empty_like(images)
+    OPS.strong_augment(images, mean, ctl, t, out)
+    return out
 
 
 class EmaTeacher:
@@ -245,13 +390,19 @@ class EmaTeacher:
         return predict_tta(self.teacher, images_t, (1.0,), False, (int(size[1]), int(size[0])),
                            return_confidence=True)
 
-    def mix(self, images, labels, images_t, sampler, num_classes=19, tau=0.968, ignore_label=255):
+    def mix(self, images, labels, images_t, sampler, num_classes=19, tau=0.968, ignore_label=255, augment=None,
+            mean=IMG_MEAN):
         """``predict`` on the target batch at the source batch's size, then ``classmix`` with ``sampler``'s keys:
-        the ``(mixed_images, mixed_labels, mixed_weights)`` a ``lambda_mix > 0`` batch ends with."""
+        the ``(mixed_images, mixed_labels, mixed_weights)`` a ``lambda_mix > 0`` batch ends with.  ``augment``: a
+        ``StrongAugSampler``; the mixed images then go through ``strong_augment`` with its next draw (labels and
+        weights stay as they are).  ``mean``: what the images had subtracted (B, G, R), for the jitter."""
         n, _, h, w = images.shape
         pred, conf = self.predict(images_t, (w, h))
-        return classmix(images, labels, images_t, pred, conf, sampler.sample(n, num_classes), num_classes, tau,
-                        ignore_label)
+        out = classmix(images, labels, images_t, pred, conf, sampler.sample(n, num_classes), num_classes, tau,
+                       ignore_label)
+        if augment is None:
+            return out
+        return (strong_augment(out[0], augment.sample(n, h, w), mean),) + out[1:]
 
     # -- checkpoints -----------------------------------------------------------------------------------
     def state_dict(self) -> dict:

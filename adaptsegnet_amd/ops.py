@@ -35,6 +35,8 @@ and, in ``MIX_NAMES``, online self-training (DACS; adaptsegnet_amd/mix.py):
   ema / ema_multi     the mean teacher's update over an arena / a list of small tensors
   classmix_*          ClassMix: per-image statistics, then selection + paste in one launch
   softmax_ce_pw_*     softmax_ce_* with a weight per pixel on the numerator
+and, in ``AUG_NAMES``, DACS's strong transform of the mixed images:
+  strong_augment      per image a colour jitter, then a Gaussian blur, one launch for the batch
 """
 from __future__ import annotations
 
@@ -202,6 +204,7 @@ def _fake(*args, **kwargs):
 NAMES: list = []        # the ops the engine and the step's own kernels launch
 LOSS_NAMES: list = []   # ops of the optional loss terms around the step (engine=False): never in an engine program
 MIX_NAMES: list = []    # ops of online self-training (adaptsegnet_amd/mix.py, names=MIX_NAMES): likewise
+AUG_NAMES: list = []    # the mixed images' colour jitter and blur (mix.strong_augment, names=AUG_NAMES): likewise
 
 
 def _op(schema, engine=True, names=None):
@@ -957,10 +960,29 @@ def _classmix_apply(images_s, labels_s, images_t, pred_t, count, nconf, keys, ig
         None if mask is None else _pt(mask, torch.uint8, (n, c), f"{what} mask"), _stream()), what)
 
 
+@_op("strong_augment(Tensor images, float[] mean, int[] ctl, Tensor table, Tensor(a!) out) -> ()", names=AUG_NAMES)
+def _strong_augment(images, mean, ctl, table, out):
+    """Colour jitter, then Gaussian blur, per image (adaptseg_strong_augment).  ``ctl``: the host copy of the
+    controls, 4 ints per image (jitter flag, order code, radius, 0).  ``table``: 16 four-byte words per image on
+    the device, three tables one after the other: the controls' bits [N, 4], (db, fc, fs, fh) [N, 4] and the half
+    kernels [N, 8]."""
+    if images.dim() != 4 or images.shape[1] != 3:
+        raise RuntimeError(f"strong_augment: images is {tuple(images.shape)}, expected [N, 3, H, W]")
+    n, _, h, w = images.shape
+    if len(mean) != 3 or len(ctl) != 4 * n:
+        raise RuntimeError(f"strong_augment: {len(mean)} means (expected 3), {len(ctl)} controls (expected {4 * n})")
+    what = "strong_augment"
+    base = _pt(table, torch.float32, (16 * n,), f"{what} table").value
+    check(_lib.lib().adaptseg_strong_augment(
+        n, h, w, _pt(images, torch.float32, (n, 3, h, w), f"{what} images"), (ctypes.c_float * 3)(*mean),
+        (ctypes.c_int32 * (4 * n))(*ctl), ctypes.c_void_p(base), ctypes.c_void_p(base + 16 * n),
+        ctypes.c_void_p(base + 32 * n), _pt(out, torch.float32, (n, 3, h, w), f"{what} out"), _stream()), what)
+
+
 class _Overloads:
     """torch.ops.adaptseg.<name>.default for every op (skips the packet's overload lookup)."""
 
 
 OPS = _Overloads()
-for _n in NAMES + LOSS_NAMES + MIX_NAMES:
+for _n in NAMES + LOSS_NAMES + MIX_NAMES + AUG_NAMES:
     setattr(OPS, _n, getattr(torch.ops.adaptseg, _n).default)

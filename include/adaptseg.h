@@ -536,6 +536,34 @@ int adaptseg_classmix_apply(int n, int h, int w, int ncls, const float *images_s
                             const int32_t *nconf, const uint32_t *keys, int ignore_label, float *mixed_images,
                             int64_t *mixed_labels, float *mixed_weights, uint8_t *mask,
                             adaptseg_stream_t stream);
+/* DACS's strong transform of the mixed images: per image a colour jitter, then a Gaussian blur,
+   each optional, ONE launch for the batch (grid (tiles, images), the block branches on its
+   image's controls).  images_in / images_out fp32 [n][3][h][w], BGR minus `mean` (HOST, 3 floats,
+   B G R).  Per image i:
+     ctl[i][4]     int32: jitter flag, order code, blur radius R, 0.  The order code holds the four
+                   ops (0 brightness, 1 contrast, 2 saturation, 3 hue) 2 bits each, first op lowest.
+     jitter[i][4]  fp32: db, fc, fs, fh
+     weights[i][8] fp32: the half kernel w[0..R], zero beyond R (normalised by the caller)
+   ctl, jitter and weights are DEVICE tables; ctl_host is the caller's HOST copy of ctl, which is
+   what the host checks read (the kernel clamps the radius it reads, so a device copy that
+   disagrees cannot reach past the image).
+     jitter: u_c = (x_c + mean_c) / 255; the ops in order on (r, g, b) = (u_2, u_1, u_0):
+             brightness clamp01(u + db), contrast clamp01(u * fc), saturation s = clamp01(s * fs) and
+             hue h = h + fh, h = h - floor(h) between rgb -> hsv and hsv -> rgb; y_c = u_c * 255 - mean_c
+     blur:   horizontal then vertical, borders reflected without repeating the edge (-1 -> 1):
+             acc = w[0] x[0]; for d = 1..R: acc = acc + w[d] (x[-d] + x[+d])
+     neither: the input's bits.
+   Every step is one fp32 operation rounded on its own (no contraction, correctly rounded
+   division): tests/strongaug_ref.py restates them in numpy and the kernel gives its bits.
+   R == 0 images: 16-byte accesses when h * w % 4 == 0 and both image pointers are 16-byte
+   aligned, scalar ones otherwise.  R > 0: 64 x 16 tiles staged with their halo in LDS.
+   Rejected on the host (ADAPTSEG_ERR_ARG) before any launch: n, h or w < 1, h * w >= 2^24,
+   n > 65535, a NULL pointer, images_out == images_in, a radius outside 0..ADAPTSEG_BLUR_MAX_RADIUS
+   or above min(h, w) - 1, an order code that is not a permutation. */
+#define ADAPTSEG_BLUR_MAX_RADIUS 7
+int adaptseg_strong_augment(int n, int h, int w, const float *images_in, const float *mean,
+                            const int32_t *ctl_host, const int32_t *ctl, const float *jitter,
+                            const float *weights, float *images_out, adaptseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Input pipeline: GTA5DataSet.__getitem__ after file decode (dataset/gta5_dataset.py:47-71) */
