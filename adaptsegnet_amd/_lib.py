@@ -65,6 +65,7 @@ FUSE_PROB, FUSE_LOGIT = 0, 1
 # adaptseg.h: the grid caps of adaptseg_ema / adaptseg_classmix_* (one sweep = blocks x 256 threads x 4 elements)
 EMA_MAX_BLOCKS, EMA_CHUNK, CLASSMIX_MAX_BLOCKS = 2048, 128, 512
 BLUR_MAX_RADIUS = 7   # adaptseg.h: the largest blur radius of adaptseg_strong_augment
+FDA_MAX_W = 4096      # adaptseg.h: the widest image of adaptseg_fda_transfer (its row twiddles sit in LDS)
 
 
 class FuseDesc(ctypes.Structure):
@@ -167,6 +168,10 @@ _SIGS = {
     "adaptseg_entropy_workspace_size": [_L, ctypes.POINTER(_SZ)],
     "adaptseg_entropy_loss_fwd": [_L, _I, _P, _P, _P, _SZ, _P],
     "adaptseg_entropy_loss_bwd": [_L, _I, _P, _P, _P, _I, _P],
+    "adaptseg_entropy_rho_loss_fwd": [_L, _I, _F, _F, _P, _P, _P, _SZ, _P],
+    "adaptseg_entropy_rho_loss_bwd": [_L, _I, _F, _F, _P, _P, _P, _I, _P],
+    "adaptseg_fda_workspace_size": [_I, _I, _I, _I, _I, ctypes.POINTER(_SZ)],
+    "adaptseg_fda_transfer": [_I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _SZ, _P],
     "adaptseg_adv_workspace_size": [_L, ctypes.POINTER(_SZ)],
     "adaptseg_adv_loss_fwd": [_L, _P, _F, _I, _P, _P, _SZ, _P],
     "adaptseg_adv_loss_bwd": [_L, _P, _F, _I, _P, _P, _I, _P],

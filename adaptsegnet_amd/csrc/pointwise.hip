@@ -699,8 +699,32 @@ __global__ void selfinfo_bwd_kernel(int64_t rows, int C, float nk, const float *
   }
 }
 
+// The robust (Charbonnier) entropy term of FDA, rho(e) = (e^2 + eps)^eta on the normalised row
+// entropy e = k H: the RHO instances of the four loss kernels below share every line of the plain
+// ones but the row's term (forward) and the row's factor d rho / d e (backward); the plain
+// instances (RHO = false) compile to the code they had.
+struct RhoArgs {
+  float k, eta, eps;   // k = 1 / ln C
+};
+
+template <bool RHO>
+__device__ __forceinline__ float ent_term(float h, const RhoArgs &ra) {
+  if (!RHO) return h;
+  const float e = ra.k * h;
+  return powf(e * e + ra.eps, ra.eta);
+}
+
+// the row's factor on -(p log p + p H): coef (= -g k / rows), times d rho / d e under RHO
+template <bool RHO>
+__device__ __forceinline__ float ent_coef(float coef, float h, const RhoArgs &ra) {
+  if (!RHO) return coef;
+  const float e = ra.k * h;
+  return coef * (2.f * ra.eta * e * powf(e * e + ra.eps, ra.eta - 1.f));
+}
+
+template <bool RHO>
 __global__ void __launch_bounds__(256) entropy_fwd_partial_kernel(int64_t rows, int C, const float *__restrict__ x,
-                                                                  float *partial) {
+                                                                  float *partial, RhoArgs ra) {
   float num = 0.f;
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows;
        r += (int64_t)gridDim.x * blockDim.x) {
@@ -712,7 +736,7 @@ __global__ void __launch_bounds__(256) entropy_fwd_partial_kernel(int64_t rows, 
       const float d = xr[c] - m;
       h -= plogp(__expf(d) * inv, d - ls);
     }
-    num += h;
+    num += ent_term<RHO>(h, ra);
   }
   __shared__ float sn[256];
   sn[threadIdx.x] = num;
@@ -728,8 +752,9 @@ __global__ void __launch_bounds__(256) entropy_fwd_partial_kernel(int64_t rows, 
 }
 
 // kr = k / rows
+template <bool RHO>
 __global__ void entropy_bwd_kernel(int64_t rows, int C, float kr, const float *__restrict__ x,
-                                   const float *__restrict__ grad_loss, float *dx, int accumulate) {
+                                   const float *__restrict__ grad_loss, float *dx, int accumulate, RhoArgs ra) {
   const float coef = -grad_loss[0] * kr;
   for (int64_t r = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; r < rows;
        r += (int64_t)gridDim.x * blockDim.x) {
@@ -742,9 +767,10 @@ __global__ void entropy_bwd_kernel(int64_t rows, int C, float kr, const float *_
       h -= plogp(__expf(d) * inv, d - ls);
     }
     float *dr = dx + r * C;
+    const float rc = ent_coef<RHO>(coef, h, ra);
     for (int c = 0; c < C; ++c) {
       const float d = xr[c] - m, p = __expf(d) * inv;
-      put(dr + c, coef * (plogp(p, d - ls) + p * h), accumulate);
+      put(dr + c, rc * (plogp(p, d - ls) + p * h), accumulate);
     }
   }
 }
@@ -815,8 +841,9 @@ __global__ void __launch_bounds__(kRowTile) selfinfo_bwd_tiled_kernel(int64_t ro
   }
 }
 
+template <bool RHO>
 __global__ void __launch_bounds__(kRowTile) entropy_fwd_tiled_kernel(int64_t rows, int C, const float *__restrict__ x,
-                                                                  float *partial) {
+                                                                  float *partial, RhoArgs ra) {
   extern __shared__ float sm[];
   __shared__ float sn[kRowTile / 64];
   float num = 0.f;
@@ -833,7 +860,7 @@ __global__ void __launch_bounds__(kRowTile) entropy_fwd_tiled_kernel(int64_t row
         const float d = v[c] - m;
         h -= plogp(__expf(d) * inv, d - ls);
       }
-      num += h;
+      num += ent_term<RHO>(h, ra);
     }
     __syncthreads();
   }
@@ -848,10 +875,11 @@ __global__ void __launch_bounds__(kRowTile) entropy_fwd_tiled_kernel(int64_t row
   }
 }
 
+template <bool RHO>
 __global__ void __launch_bounds__(kRowTile) entropy_bwd_tiled_kernel(int64_t rows, int C, float kr,
                                                                   const float *__restrict__ x,
                                                                   const float *__restrict__ grad_loss, float *dx,
-                                                                  int accumulate) {
+                                                                  int accumulate, RhoArgs ra) {
   extern __shared__ float sm[];
   const float coef = -grad_loss[0] * kr;
   for (int64_t r0 = (int64_t)blockIdx.x * kRowTile; r0 < rows; r0 += (int64_t)gridDim.x * kRowTile) {
@@ -868,9 +896,10 @@ __global__ void __launch_bounds__(kRowTile) entropy_bwd_tiled_kernel(int64_t row
         const float d = v[c] - m;
         h -= plogp(__expf(d) * inv, d - ls);
       }
+      const float rc = ent_coef<RHO>(coef, h, ra);
       for (int c = 0; c < C; ++c) {
         const float d = v[c] - m, p = __expf(d) * inv;
-        v[c] = coef * (plogp(p, d - ls) + p * h);
+        v[c] = rc * (plogp(p, d - ls) + p * h);
       }
     }
     __syncthreads();
@@ -1648,39 +1677,73 @@ int adaptseg_entropy_workspace_size(int64_t rows, size_t *bytes) {
   return ADAPTSEG_OK;
 }
 
-int adaptseg_entropy_loss_fwd(int64_t rows, int c, const float *x, float *loss, void *ws, size_t ws_bytes,
-                              adaptseg_stream_t stream) {
-  AS_CHECK_ARG(rows > 0 && c >= 2 && x && loss, "entropy_loss_fwd: bad args (rows > 0, c >= 2, non-NULL x / loss)");
+// the plain loss (RHO = false: k mean H) and the robust one (mean (e^2 + eps)^eta) on the same launches
+extern "C++" {
+template <bool RHO>
+static int entropy_fwd_launch(const char *name, int64_t rows, int c, RhoArgs ra, const float *x, float *loss, void *ws,
+                              size_t ws_bytes, adaptseg_stream_t stream) {
   const int parts = entropy_parts(rows);
   if (!ws || ws_bytes < (size_t)parts * 2 * sizeof(float)) {
-    set_error("entropy_loss_fwd: workspace too small");
+    set_error("%s: workspace too small", name);
     return ADAPTSEG_ERR_WORKSPACE;
   }
   hipStream_t s = as_stream(stream);
   float *partial = reinterpret_cast<float *>(ws);
   if (c <= kRowTileMaxC)
-    entropy_fwd_tiled_kernel<<<parts, kRowTile, kRowTile * c * sizeof(float), s>>>(rows, c, x, partial);
+    entropy_fwd_tiled_kernel<RHO><<<parts, kRowTile, kRowTile * c * sizeof(float), s>>>(rows, c, x, partial, ra);
   else
-    entropy_fwd_partial_kernel<<<parts, 256, 0, s>>>(rows, c, x, partial);
+    entropy_fwd_partial_kernel<RHO><<<parts, 256, 0, s>>>(rows, c, x, partial, ra);
   AS_CHECK_LAUNCH("entropy_fwd_partial");
-  pair_final_kernel<<<1, 64, 0, s>>>(partial, parts, loss, 1, inv_ln(c) / (double)rows);
+  pair_final_kernel<<<1, 64, 0, s>>>(partial, parts, loss, 1, (RHO ? 1.0 : inv_ln(c)) / (double)rows);
   AS_CHECK_LAUNCH("entropy_final");
   return ADAPTSEG_OK;
+}
+
+template <bool RHO>
+static int entropy_bwd_launch(int64_t rows, int c, RhoArgs ra, const float *x, const float *grad_loss, float *dx,
+                              int flags, adaptseg_stream_t stream) {
+  const float kr = (float)(inv_ln(c) / (double)rows);
+  const int acc = (flags & ADAPTSEG_EPI_ACCUMULATE) ? 1 : 0;
+  if (c <= kRowTileMaxC)
+    entropy_bwd_tiled_kernel<RHO><<<grid1d(rows, kRowTile, 8192), kRowTile, kRowTile * c * sizeof(float),
+                                    as_stream(stream)>>>(rows, c, kr, x, grad_loss, dx, acc, ra);
+  else
+    entropy_bwd_kernel<RHO><<<grid1d(rows), 256, 0, as_stream(stream)>>>(rows, c, kr, x, grad_loss, dx, acc, ra);
+  AS_CHECK_LAUNCH("entropy_bwd");
+  return ADAPTSEG_OK;
+}
+}  // extern "C++"
+
+int adaptseg_entropy_loss_fwd(int64_t rows, int c, const float *x, float *loss, void *ws, size_t ws_bytes,
+                              adaptseg_stream_t stream) {
+  AS_CHECK_ARG(rows > 0 && c >= 2 && x && loss, "entropy_loss_fwd: bad args (rows > 0, c >= 2, non-NULL x / loss)");
+  return entropy_fwd_launch<false>("entropy_loss_fwd", rows, c, RhoArgs{0.f, 0.f, 0.f}, x, loss, ws, ws_bytes, stream);
 }
 
 int adaptseg_entropy_loss_bwd(int64_t rows, int c, const float *x, const float *grad_loss, float *dx, int flags,
                               adaptseg_stream_t stream) {
   AS_CHECK_ARG(rows > 0 && c >= 2 && x && grad_loss && dx,
                "entropy_loss_bwd: bad args (rows > 0, c >= 2, non-NULL x / grad_loss / dx)");
-  const float kr = (float)(inv_ln(c) / (double)rows);
-  const int acc = (flags & ADAPTSEG_EPI_ACCUMULATE) ? 1 : 0;
-  if (c <= kRowTileMaxC)
-    entropy_bwd_tiled_kernel<<<grid1d(rows, kRowTile, 8192), kRowTile, kRowTile * c * sizeof(float),
-                               as_stream(stream)>>>(rows, c, kr, x, grad_loss, dx, acc);
-  else
-    entropy_bwd_kernel<<<grid1d(rows), 256, 0, as_stream(stream)>>>(rows, c, kr, x, grad_loss, dx, acc);
-  AS_CHECK_LAUNCH("entropy_bwd");
-  return ADAPTSEG_OK;
+  return entropy_bwd_launch<false>(rows, c, RhoArgs{0.f, 0.f, 0.f}, x, grad_loss, dx, flags, stream);
+}
+
+static bool rho_ok(float eta, float eps) { return eta > 0.f && eta <= 16.f && eps > 0.f && eps <= 1.f; }
+
+int adaptseg_entropy_rho_loss_fwd(int64_t rows, int c, float eta, float eps, const float *x, float *loss, void *ws,
+                                  size_t ws_bytes, adaptseg_stream_t stream) {
+  AS_CHECK_ARG(rows > 0 && c >= 2 && x && loss,
+               "entropy_rho_loss_fwd: bad args (rows > 0, c >= 2, non-NULL x / loss)");
+  AS_CHECK_ARG(rho_ok(eta, eps), "entropy_rho_loss_fwd: bad eta %g or eps %g (0 < eta <= 16, 0 < eps <= 1)", eta, eps);
+  return entropy_fwd_launch<true>("entropy_rho_loss_fwd", rows, c, RhoArgs{(float)inv_ln(c), eta, eps}, x, loss, ws,
+                                  ws_bytes, stream);
+}
+
+int adaptseg_entropy_rho_loss_bwd(int64_t rows, int c, float eta, float eps, const float *x, const float *grad_loss,
+                                  float *dx, int flags, adaptseg_stream_t stream) {
+  AS_CHECK_ARG(rows > 0 && c >= 2 && x && grad_loss && dx,
+               "entropy_rho_loss_bwd: bad args (rows > 0, c >= 2, non-NULL x / grad_loss / dx)");
+  AS_CHECK_ARG(rho_ok(eta, eps), "entropy_rho_loss_bwd: bad eta %g or eps %g (0 < eta <= 16, 0 < eps <= 1)", eta, eps);
+  return entropy_bwd_launch<true>(rows, c, RhoArgs{(float)inv_ln(c), eta, eps}, x, grad_loss, dx, flags, stream);
 }
 
 static int adv_parts(int64_t n) { return grid1d(n, 256 * 4, 256); }

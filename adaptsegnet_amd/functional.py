@@ -10,7 +10,8 @@ Tensors at this boundary are NCHW-shaped, as in the reference; internally they a
   nn.Upsample(bilinear, align_corners=True)     train_gta2cityscapes_multi.py:237-238 (interp),
                                                 model/deeplab_multi.py:188-189
 Beyond the reference: ``selfinfo2d`` and ``entropy_loss2d``, the two halves of entropy-based
-adaptation (ADVENT), each fused from the logits.
+adaptation (ADVENT), each fused from the logits; ``entropy_loss2d(x, eta=...)`` is
+FDA's robust entropy term on the same kernels.
 """
 from __future__ import annotations
 
@@ -86,14 +87,38 @@ class _EntropyLoss2d(torch.autograd.Function):
         return K.as_nchw(K.entropy_bwd(xv, g.contiguous()))
 
 
-def entropy_loss2d(x: torch.Tensor) -> torch.Tensor:
+class _EntropyRhoLoss2d(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, eta, eps):
+        xv = K.nhwc_view(x)
+        ctx.save_for_backward(xv)
+        ctx.eta, ctx.eps = eta, eps
+        return K.entropy_rho_fwd(xv, eta, eps)[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        (xv,) = ctx.saved_tensors
+        if g.dim() == 0:
+            g = g.reshape(1)
+        return K.as_nchw(K.entropy_rho_bwd(xv, ctx.eta, ctx.eps, g.contiguous())), None, None
+
+
+def entropy_loss2d(x: torch.Tensor, eta: float | None = None, eps: float = 1e-8) -> torch.Tensor:
     """The entropy-minimisation loss of [N, C, H, W] logits (ADVENT's MinEnt): the mean over pixels
     of ``-sum_c p log p``, divided by ``ln C`` (1 for a uniform prediction, 0 for a one-hot one).
-    Returns a 0-dim device tensor; deterministic (block partials + one ordered fp64 sum)."""
+    With ``eta``: FDA's robust form, the mean over pixels of ``(e^2 + eps)^eta`` with ``e`` that
+    normalised pixel entropy (a Charbonnier penalty; FDA trains with ``eta = 2``); ``eta=None`` is
+    the plain loss on its own kernels, and ``eps`` is then unused.  Returns a 0-dim device tensor;
+    deterministic (block partials + one ordered fp64 sum); the backward keeps only the logits."""
     _check(x, "entropy_loss2d")
     if x.dim() != 4 or x.shape[1] < 2:
         raise RuntimeError(f"entropy_loss2d: expected [N, C, H, W] logits with C >= 2, got {tuple(x.shape)}")
-    return _EntropyLoss2d.apply(x)
+    if eta is None:
+        return _EntropyLoss2d.apply(x)
+    eta, eps = float(eta), float(eps)
+    if not (0.0 < eta <= 16.0 and 0.0 < eps <= 1.0):
+        raise ValueError(f"entropy_loss2d: eta {eta!r}, eps {eps!r} (expected 0 < eta <= 16 and 0 < eps <= 1)")
+    return _EntropyRhoLoss2d.apply(x, eta, eps)
 
 
 class _CrossEntropy2d(torch.autograd.Function):

@@ -26,7 +26,7 @@ __all__ = [
     "ConvGeom", "set_conv_math", "get_conv_math", "MATH_F32", "MATH_BF16", "MATH_BF16_WIDE", "MATH_F32X3", "MATH_F32X3_PRESPLIT", "conv_fwd", "conv_fwd_bnstats", "conv_dgrad", "conv_wgrad", "bn_fwd_train",
     "bn_fwd_train_tiles", "bn_fwd_infer", "bn_bwd", "conv_fwd_all", "conv_dgrad_all", "bn_fwd_train_all", "bn_fwd_infer_all", "bn_bwd_all",
     "maxpool_fwd", "maxpool_bwd", "upsample_fwd", "upsample_bwd", "softmax_fwd", "softmax_bwd",
-    "ce_fwd", "ce_bwd", "selfinfo_fwd", "selfinfo_bwd", "entropy_fwd", "entropy_bwd", "adv_fwd", "adv_bwd", "sgd_step", "adam_step", "zero_", "to_nhwc",
+    "ce_fwd", "ce_bwd", "selfinfo_fwd", "selfinfo_bwd", "entropy_fwd", "entropy_bwd", "entropy_rho_fwd", "entropy_rho_bwd", "adv_fwd", "adv_bwd", "sgd_step", "adam_step", "zero_", "to_nhwc",
     "axpy", "add_i64", "weight_pack_scope", "pack_builds", "pack_count", "clear_weight_packs", "EPI_ACCUMULATE", "EPI_LEAKY", "EPI_LEAKY_GRAD", "EPI_RELU", "EPI_RELU_GRAD", "EPI_RESIDUAL",
 ]
 
@@ -729,6 +729,21 @@ def entropy_bwd(x, grad_loss, dx=None, accumulate=False):
     if dx is None:
         dx = torch.empty_like(x)
     _OP.entropy_loss_bwd(x, grad_loss, dx, bool(accumulate))
+    return dx
+
+
+def entropy_rho_fwd(x, eta: float, eps: float):
+    """mean over rows of ((H / ln C)^2 + eps)^eta, H the row entropy of the logits x [..., C] (FDA's robust
+    entropy term): a 1-element device tensor."""
+    loss = torch.empty(1, device=x.device, dtype=torch.float32)
+    _OP.entropy_rho_loss_fwd(x, float(eta), float(eps), loss)
+    return loss
+
+
+def entropy_rho_bwd(x, eta: float, eps: float, grad_loss, dx=None, accumulate=False):
+    if dx is None:
+        dx = torch.empty_like(x)
+    _OP.entropy_rho_loss_bwd(x, float(eta), float(eps), grad_loss, dx, bool(accumulate))
     return dx
 
 

@@ -37,6 +37,9 @@ and, in ``MIX_NAMES``, online self-training (DACS; adaptsegnet_amd/mix.py):
   softmax_ce_pw_*     softmax_ce_* with a weight per pixel on the numerator
 and, in ``AUG_NAMES``, DACS's strong transform of the mixed images:
   strong_augment      per image a colour jitter, then a Gaussian blur, one launch for the batch
+and, in ``FDA_NAMES``, Fourier Domain Adaptation (adaptsegnet_amd/fda.py):
+  fda_transfer        a source batch with the low-frequency amplitude spectrum of a target batch
+  entropy_rho_loss_*  entropy_loss_* with FDA's robust penalty ((H / ln C)^2 + eps)^eta per pixel
 """
 from __future__ import annotations
 
@@ -205,6 +208,7 @@ NAMES: list = []        # the ops the engine and the step's own kernels launch
 LOSS_NAMES: list = []   # ops of the optional loss terms around the step (engine=False): never in an engine program
 MIX_NAMES: list = []    # ops of online self-training (adaptsegnet_amd/mix.py, names=MIX_NAMES): likewise
 AUG_NAMES: list = []    # the mixed images' colour jitter and blur (mix.strong_augment, names=AUG_NAMES): likewise
+FDA_NAMES: list = []    # FDA's spectral transfer and robust entropy term (adaptsegnet_amd/fda.py, names=FDA_NAMES): likewise
 
 
 def _op(schema, engine=True, names=None):
@@ -979,10 +983,58 @@ def _strong_augment(images, mean, ctl, table, out):
         ctypes.c_void_p(base + 32 * n), _pt(out, torch.float32, (n, 3, h, w), f"{what} out"), _stream()), what)
 
 
+# ---- Fourier Domain Adaptation (adaptsegnet_amd/fda.py, functional.entropy_loss2d(eta=...)) --------
+@_op("fda_transfer(Tensor src, Tensor trg, int b, Tensor? mean, Tensor tw_w, Tensor tw_h, Tensor(a!) out) -> ()",
+     names=FDA_NAMES)
+def _fda_transfer(src, trg, b, mean, tw_w, tw_h, out):
+    """out = src with the low-frequency amplitudes (|u|, |v| <= b) of trg (adaptseg_fda_transfer).  ``mean``: float32
+    [C] on the device or None; ``tw_w`` / ``tw_h``: the (cos, sin) tables float32 [W, 2] / [H, 2] (fda.twiddles)."""
+    if src.dim() != 4:
+        raise RuntimeError(f"fda_transfer: src is {tuple(src.shape)}, expected [N, C, H, W]")
+    n, c, h, w = src.shape
+    what = "fda_transfer"
+    b = int(b)
+    sz = ctypes.c_size_t(0)
+    check(_lib.lib().adaptseg_fda_workspace_size(n, c, h, w, b, ctypes.byref(sz)), "fda_workspace_size")
+    wp, wsz = _ws_args(sz.value, src.device)
+    check(_lib.lib().adaptseg_fda_transfer(
+        n, c, h, w, b, _pt(src, torch.float32, (n, c, h, w), f"{what} src"),
+        _pt(trg, torch.float32, (n, c, h, w), f"{what} trg"),
+        None if mean is None else _pt(mean, torch.float32, (c,), f"{what} mean"),
+        _pt(tw_w, torch.float32, (w, 2), f"{what} tw_w"), _pt(tw_h, torch.float32, (h, 2), f"{what} tw_h"),
+        _pt(out, torch.float32, (n, c, h, w), f"{what} out"), wp, wsz, _stream()), what)
+
+
+@_op("entropy_rho_loss_fwd(Tensor x, float eta, float eps, Tensor(a!) loss) -> ()", names=FDA_NAMES)
+def _entropy_rho_loss_fwd(x, eta, eps, loss):
+    """entropy_loss_fwd with FDA's robust term: loss = mean over rows of ((H / ln c)^2 + eps)^eta."""
+    rows, c = _rc(x)
+    b = ctypes.c_size_t(0)
+    check(_lib.lib().adaptseg_entropy_workspace_size(rows, ctypes.byref(b)), "entropy_workspace_size")
+    wp, wsz = _ws_args(b.value, x.device)
+    check(_lib.lib().adaptseg_entropy_rho_loss_fwd(rows, c, float(eta), float(eps),
+                                                   _pf(x, rows * c, "entropy_rho_loss_fwd x"),
+                                                   _pf(loss, 1, "entropy_rho_loss_fwd loss"), wp, wsz, _stream()),
+          "entropy_rho_loss_fwd")
+
+
+@_op("entropy_rho_loss_bwd(Tensor x, float eta, float eps, Tensor grad_loss, Tensor(a!) dx, bool accumulate) -> ()",
+     names=FDA_NAMES)
+def _entropy_rho_loss_bwd(x, eta, eps, grad_loss, dx, accumulate):
+    rows, c = _rc(x)
+    n = rows * c
+    check(_lib.lib().adaptseg_entropy_rho_loss_bwd(rows, c, float(eta), float(eps),
+                                                   _pf(x, n, "entropy_rho_loss_bwd x"),
+                                                   _pf(grad_loss, 1, "entropy_rho_loss_bwd grad_loss"),
+                                                   _pf(dx, n, "entropy_rho_loss_bwd dx"),
+                                                   _lib.EPI_ACCUMULATE if accumulate else 0, _stream()),
+          "entropy_rho_loss_bwd")
+
+
 class _Overloads:
     """torch.ops.adaptseg.<name>.default for every op (skips the packet's overload lookup)."""
 
 
 OPS = _Overloads()
-for _n in NAMES + LOSS_NAMES + MIX_NAMES + AUG_NAMES:
+for _n in NAMES + LOSS_NAMES + MIX_NAMES + AUG_NAMES + FDA_NAMES:
     setattr(OPS, _n, getattr(torch.ops.adaptseg, _n).default)

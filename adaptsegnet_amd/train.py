@@ -89,6 +89,10 @@ class StepConfig:
     # weighting of head 1); batches keep their shape.  The defaults are the step as it was
     d_input: str = "softmax"
     lambda_ent: float = 0.0
+    # FDA's robust entropy term: with ent_eta the lambda_ent term is entropy_loss2d(pred, eta=ent_eta), the
+    # mean over pixels of (e^2 + 1e-8)^ent_eta on the normalised pixel entropy e (FDA: lambda_ent = 0.005,
+    # ent_eta = 2.0).  It shapes lambda_ent's term, so it needs lambda_ent > 0.  None: the plain entropy loss
+    ent_eta: float | None = None
     # online self-training (DACS: mean teacher + ClassMix, adaptsegnet_amd/mix.py).  With
     # lambda_mix > 0 every batch ends with three more elements, after the optional labels_target:
     # (mixed_images float32 [N, 3, H, W], mixed_labels int64 [N, H, W], mixed_weights float32
@@ -135,6 +139,11 @@ class StepConfig:
     # for DeeplabMulti, the caller's stream for DeeplabVGG); see step()
     main_priority: int | str | None = "auto"
 
+    def __post_init__(self):
+        if self.ent_eta is not None and not self.lambda_ent > 0:
+            raise ValueError(f"ent_eta {self.ent_eta!r} with lambda_ent {self.lambda_ent!r}: ent_eta shapes the "
+                             "entropy term, which lambda_ent > 0 turns on")
+
 
 @dataclass
 class StepLosses:
@@ -172,6 +181,9 @@ class AdaptSegTrainer:
         if cfg.lambda_ent > 0 and cfg.level == "source-only":
             raise ValueError("lambda_ent > 0: the entropy term belongs to the target branch of the "
                              "single-level / multi-level steps; the source-only step has none")
+        cfg.__post_init__()   # ent_eta needs lambda_ent > 0 (a config changed after it was made)
+        if cfg.ent_eta is not None and not 0.0 < cfg.ent_eta <= 16.0:
+            raise ValueError(f"ent_eta {cfg.ent_eta!r} (expected None or 0 < ent_eta <= 16)")
         if cfg.lambda_mix < 0:
             raise ValueError(f"lambda_mix {cfg.lambda_mix!r} (expected >= 0)")
         if cfg.lambda_mix > 0 and warper is not None:
@@ -286,8 +298,8 @@ class AdaptSegTrainer:
         return F.selfinfo2d(pred) if self.cfg.d_input == "entropy" else F.softmax2d(pred)
 
     def _ent_loss(self, pred_target):
-        """[entropy_loss2d(pred_target)] with lambda_ent > 0, else []."""
-        return [F.entropy_loss2d(pred_target)] if self.cfg.lambda_ent > 0 else []
+        """[entropy_loss2d(pred_target)] (FDA's robust form with cfg.ent_eta) with lambda_ent > 0, else []."""
+        return [F.entropy_loss2d(pred_target, eta=self.cfg.ent_eta)] if self.cfg.lambda_ent > 0 else []
 
     def _d_again(self, D, pred, keep):
         """D on the detached target prediction for D's own step: the kept forward when there is one."""

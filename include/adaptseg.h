@@ -564,6 +564,31 @@ int adaptseg_classmix_apply(int n, int h, int w, int ncls, const float *images_s
 int adaptseg_strong_augment(int n, int h, int w, const float *images_in, const float *mean,
                             const int32_t *ctl_host, const int32_t *ctl, const float *jitter,
                             const float *weights, float *images_out, adaptseg_stream_t stream);
+/* FDA spectral transfer (Yang & Soatto, CVPR 2020): image i of src takes the low-frequency
+   amplitude spectrum of image i of trg, its phase stays.  src / trg / out fp32 [n][c][h][w];
+   the window is |u|, |v| <= b.  With S, T the DFTs of src + mean[ch] and trg + mean[ch]:
+     out = src + (1 / hw) sum_{|u|,|v|<=b} D(u,v) e^{+2 pi i (uy/h + vx/w)}
+     D   = (|T| - |S|) S / |S|        (S / |S| = 1 where S == 0)
+   which is Re(ifft2) of the spectrum with the window's amplitudes swapped, minus mean.  Only the
+   DC coefficient sees the mean.  mean: DEVICE fp32 [c] or NULL (zeros).  tw_w / tw_h: DEVICE
+   tables fp32 [w][2] / [h][2] of (cos, sin)(2 pi k / w) and (2 pi k / h), 8-byte aligned; the
+   kernels index them with integers, no sine or cosine is evaluated on the device.
+   Four launches, no host synchronisation, no atomics:
+     rows    R(y,v) = sum_x img e^{-2 pi i vx/w}, v = 0..b, both images: fp32 sums over 256-column
+             chunks in column order, chunk sums added in fp64
+     cols    F(u,v) = sum_y R e^{-2 pi i uy/h} in fp64 (four row slices, added in order), then D
+     g       G(y,v) = sum_u D e^{+2 pi i uy/h} in fp64, u ascending
+     apply   out = src + sum_v w_v Re(G e^{+2 pi i vx/w}) / hw, fp32, v descending (w_0 = 1, else 2)
+   Every sum has a fixed order and reads one image-channel: the same bits every run, whatever n.
+   ws: adaptseg_fda_workspace_size bytes (the row-stage intermediates, G and D), 8-byte aligned.
+   trg may be src.  Rejected on the host before any launch: n, c, h, w < 1, h * w >= 2^24,
+   w > 4096, n * c > 65535, b < 0 or 2 b + 1 > min(h, w), a NULL pointer, misaligned tables, out
+   overlapping src or trg (ADAPTSEG_ERR_ARG); a NULL, misaligned or short ws
+   (ADAPTSEG_ERR_WORKSPACE). */
+int adaptseg_fda_workspace_size(int n, int c, int h, int w, int b, size_t *bytes);
+int adaptseg_fda_transfer(int n, int c, int h, int w, int b, const float *src, const float *trg,
+                          const float *mean, const float *tw_w, const float *tw_h, float *out,
+                          void *ws, size_t ws_bytes, adaptseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Input pipeline: GTA5DataSet.__getitem__ after file decode (dataset/gta5_dataset.py:47-71) */
@@ -683,6 +708,18 @@ int adaptseg_entropy_loss_fwd(int64_t rows, int c, const float *x, float *loss, 
                               size_t ws_bytes, adaptseg_stream_t stream);
 int adaptseg_entropy_loss_bwd(int64_t rows, int c, const float *x, const float *grad_loss,
                               float *dx, int flags, adaptseg_stream_t stream);
+/* FDA's robust entropy term (a Charbonnier penalty on the normalised row entropy e = k H):
+     loss[0] = mean_rows (e^2 + eps)^eta
+     dx      = (grad_loss[0] / rows) 2 eta e (e^2 + eps)^(eta - 1) k (-(p log p + p H))
+   The same kernels as the plain loss (a template parameter), the same block partials in a
+   workspace of adaptseg_entropy_workspace_size and the same fixed-order fp64 finish; the
+   backward reads nothing but x.  Rejected on the host as above, and eta outside (0, 16] or eps
+   outside (0, 1] (NaN included) with ADAPTSEG_ERR_ARG. */
+int adaptseg_entropy_rho_loss_fwd(int64_t rows, int c, float eta, float eps, const float *x,
+                                  float *loss, void *ws, size_t ws_bytes, adaptseg_stream_t stream);
+int adaptseg_entropy_rho_loss_bwd(int64_t rows, int c, float eta, float eps, const float *x,
+                                  const float *grad_loss, float *dx, int flags,
+                                  adaptseg_stream_t stream);
 
 /* ------------------------------------------------------------------------------------ */
 /* Adversarial losses against a constant target (train_gta2cityscapes_multi.py:542-545, */
