@@ -24,8 +24,17 @@ returns to the host between the teacher's forward and the step:
   optional, in one launch for the batch (csrc/strongaug.hip).  The host draws the parameters and the
   blur's half kernel; the device runs fp32 ``+ - * / floor``, compares and selects only.
 
-tests/classmix_ref.py and tests/strongaug_ref.py restate the rules in numpy; tests/test_classmix_gpu.py and
-tests/test_strongaug_gpu.py compare bit for bit.
+* ``mask_patches`` / ``EmaTeacher.mask(images_t, PatchMaskSampler())``: Masked Image Consistency (MIC, Hoyer et
+  al., CVPR 2023), the stage built on DACS.  The student sees the target image with random square patches set
+  to 0 (the mean colour of this image space) and must reproduce the labels the teacher gave the WHOLE image,
+  weighted by ``q`` (``StepConfig.lambda_mic``).  Two launches (csrc/mic.hip): ``conf_count``, ClassMix's
+  ``nconf`` on its own (skipped when the caller passes ClassMix's), and ``patch_mask``: a patch is masked iff
+  its uint32 key (``PatchMaskSampler``, one per patch) is below ``floor(ratio * 2^32)``, the labels are the
+  teacher's classes and are not masked, the weights are ``q`` with ``ignore_top`` / ``ignore_bottom`` rows
+  zeroed (DAFormer's ``pseudo_weight_ignore_top / bottom``: the rows still count in ``nconf`` and ``H * W``).
+
+tests/classmix_ref.py, tests/strongaug_ref.py and tests/mic_ref.py restate the rules in numpy;
+tests/test_classmix_gpu.py, tests/test_strongaug_gpu.py and tests/test_mic_gpu.py compare bit for bit.
 
 Deliberate differences from DACS:
 
@@ -37,6 +46,15 @@ Deliberate differences from DACS:
 * The blur has one radius, ``min(ceil(6 sigma), (ceil(0.1 min(H, W)) - 1) // 2)``: DACS's kernel-size rule
   applied to the shorter side where DACS sizes each axis on its own (the two coincide once both sides are
   >= 141), and trimmed to the taps that matter in fp32 (the mass beyond 6 sigma is below 2^-24 of the sum).
+
+Deliberate differences from MIC's code:
+
+* The patch grid has ``ceil(H / patch)`` x ``ceil(W / patch)`` cells and pixel (y, x) belongs to cell ``(y //
+  patch, x // patch)``; MIC draws ``round(H / b)`` cells and stretches them with a nearest resize.  The two
+  coincide when ``patch`` divides H and W.
+* ``q`` is per image, not per batch, for the reason given above.
+* The loss's mean is ``mean_or_zero`` over the valid pixels, like every other CE term of the step.
+* The keys come from the host (PCG64, resumable), not from ``torch.rand`` on the device.
 """
 from __future__ import annotations
 
@@ -66,17 +84,19 @@ def _check_alpha(alpha):
         raise ValueError(f"EMA alpha {alpha!r} (expected 0 <= alpha <= 1)")
 
 
-def _keys_tensor(keys, n, c, device):
-    """The uint32 [n, c] keys as an int32 device tensor of the same bits (pinned staging: no sync)."""
+def _keys_tensor(keys, shape, device, what="classmix"):
+    """The uint32 keys of ``shape`` as an int32 device tensor of the same bits (pinned staging: no sync)."""
     if isinstance(keys, np.ndarray):
-        if keys.dtype != np.uint32 or keys.shape != (n, c):
-            raise ValueError(f"classmix: keys are {keys.dtype} {keys.shape}, expected uint32 {(n, c)}")
+        if keys.dtype != np.uint32 or keys.shape != shape:
+            raise ValueError(f"{what}: keys are {keys.dtype} {keys.shape}, expected uint32 {shape}")
         t = torch.from_numpy(np.ascontiguousarray(keys).view(np.int32))
         if torch.device(device).type == "cuda":
             t = t.pin_memory()
         return t.to(device, non_blocking=True)
-    if keys.dtype not in (torch.int32, torch.uint32) or tuple(keys.shape) != (n, c):
-        raise ValueError(f"classmix: keys are {keys.dtype} {tuple(keys.shape)}, expected uint32 / int32 {(n, c)}")
+    if not isinstance(keys, torch.Tensor) or keys.dtype not in (torch.int32, torch.uint32) \
+            or tuple(keys.shape) != shape:
+        got = f"{keys.dtype} {tuple(keys.shape)}" if isinstance(keys, torch.Tensor) else type(keys).__name__
+        raise ValueError(f"{what}: keys are {got}, expected uint32 / int32 {shape}")
     return keys.contiguous().view(torch.int32).to(device)
 
 
@@ -106,7 +126,7 @@ def classmix(images_s, labels_s, images_t, pred_t, conf_t, keys, num_classes=19,
     if h * w >= 1 << 24:
         raise ValueError(f"classmix: {h} x {w} pixels per image (expected H * W < 2^24)")
     dev = images_s.device
-    keys = _keys_tensor(keys, n, c, dev)   # checked before anything is launched
+    keys = _keys_tensor(keys, (n, c), dev)   # checked before anything is launched
     images_s, labels_s, images_t = images_s.contiguous(), labels_s.contiguous(), images_t.contiguous()
     pred_t, conf_t = pred_t.contiguous(), conf_t.contiguous()
     count = torch.empty((n, c), dtype=torch.int32, device=dev)
@@ -278,6 +298,104 @@ def strong_augment(images: torch.Tensor, params: dict, mean=IMG_MEAN) -> torch.T
     return out
 
 
+def mask_threshold(ratio: float) -> int:
+    """``floor(ratio * 2^32)``, exact in fp64: a patch is masked iff its uint32 key is below it."""
+    ratio = float(ratio)
+    if not 0.0 <= ratio <= 1.0:
+        raise ValueError(f"mask ratio {ratio!r} (expected 0 <= ratio <= 1)")
+    return int(math.floor(ratio * 4294967296.0))
+
+
+def _check_patch(patch):
+    if isinstance(patch, bool) or int(patch) != patch or int(patch) < 1:
+        raise ValueError(f"mask patch {patch!r} (expected an integer, at least 1)")
+    return int(patch)
+
+
+def mask_patches(images_t, pred_t, conf_t, keys, patch=64, ratio=0.7, num_classes=19, tau=0.968, ignore_label=255,
+                 ignore_top=0, ignore_bottom=0, nconf=None):
+    """MIC's masked target batch and the teacher's labels of the whole images.
+
+    images_t: float32 [N, 3, H, W]; pred_t (uint8) and conf_t (float32) [N, H, W]: ``EmaTeacher.predict``; keys:
+    uint32 [N, ceil(H / patch), ceil(W / patch)] (``PatchMaskSampler.sample``).  Returns ``(masked_images,
+    masked_labels, masked_weights)`` — float32 [N, 3, H, W], int64 [N, H, W], float32 [N, H, W]: the images with
+    every patch whose key is below ``floor(ratio * 2^32)`` set to 0 (the mean colour), the teacher's classes
+    (``ignore_label`` from ``num_classes`` on; not masked), and ``q = nconf / (H * W)`` with the first
+    ``ignore_top`` and the last ``ignore_bottom`` rows zeroed.  ``nconf``: int32 [N], the pixels with ``conf_t >=
+    tau``, e.g. from ``classmix(..., return_stats=True)`` on the same teacher output and ``tau``; the count launch
+    is then skipped (``conf_t`` and ``tau`` are not read).  Any memory layout is accepted (a non-contiguous
+    input is copied first); what is wrong raises on the host, before any launch."""
+    patch = _check_patch(patch)
+    threshold = mask_threshold(ratio)
+    c = int(num_classes)
+    if not 1 <= c <= 256:
+        raise ValueError(f"mask_patches: num_classes {num_classes!r} (expected 1..256)")
+    if not 0 <= int(ignore_label) <= 255:
+        raise ValueError(f"mask_patches: ignore_label {ignore_label!r} (expected 0..255)")
+    top, bottom = int(ignore_top), int(ignore_bottom)
+    if top < 0 or bottom < 0 or top != ignore_top or bottom != ignore_bottom:
+        raise ValueError(f"mask_patches: ignore_top {ignore_top!r}, ignore_bottom {ignore_bottom!r} (expected "
+                         "integers, at least 0)")
+    if images_t.dim() != 4 or images_t.shape[1] != 3 or images_t.dtype != torch.float32:
+        raise RuntimeError(f"mask_patches: images_t is {images_t.dtype} {tuple(images_t.shape)}, expected float32 "
+                           "[N, 3, H, W]")
+    n, _, h, w = images_t.shape
+    if n < 1 or h < 1 or w < 1 or h * w >= 1 << 24 or n > 65535:
+        raise ValueError(f"mask_patches: {n} images of {h} x {w} pixels (expected 1 <= N <= 65535, H, W >= 1, "
+                         "H * W < 2^24)")
+    if pred_t.dtype != torch.uint8 or tuple(pred_t.shape) != (n, h, w):
+        raise ValueError(f"mask_patches: pred_t is {pred_t.dtype} {tuple(pred_t.shape)}, expected uint8 {(n, h, w)}")
+    dev = images_t.device
+    if nconf is None:
+        if conf_t.dtype != torch.float32 or tuple(conf_t.shape) != (n, h, w):
+            raise ValueError(f"mask_patches: conf_t is {conf_t.dtype} {tuple(conf_t.shape)}, expected float32 "
+                             f"{(n, h, w)}")
+    elif not isinstance(nconf, torch.Tensor) or nconf.dtype != torch.int32 or tuple(nconf.shape) != (n,) \
+            or nconf.device != dev:
+        got = f"{nconf.dtype} {tuple(nconf.shape)} on {nconf.device}" if isinstance(nconf, torch.Tensor) \
+            else type(nconf).__name__
+        raise ValueError(f"mask_patches: nconf is {got}, expected int32 {(n,)} on {dev}")
+    keys = _keys_tensor(keys, (n, -(-h // patch), -(-w // patch)), dev, "mask_patches")   # before any launch
+    images_t, pred_t = images_t.contiguous(), pred_t.contiguous()
+    if nconf is None:
+        nconf = torch.empty((n,), dtype=torch.int32, device=dev)
+        OPS.conf_count(conf_t.contiguous(), float(tau), nconf)
+    masked_images = torch.empty_like(images_t)
+    labels = torch.empty((n, h, w), dtype=torch.int64, device=dev)
+    weights = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+    OPS.patch_mask(images_t, pred_t, nconf.contiguous(), keys, patch, threshold, c, int(ignore_label), top, bottom,
+                   masked_images, labels, weights)
+    return masked_images, labels, weights
+
+
+class PatchMaskSampler:
+    """Draws MIC's per-patch uint32 keys on the host: a patch is masked iff its key is below ``threshold`` =
+    ``floor(ratio * 2^32)``, so every patch is masked with probability ``ratio`` on its own (MIC's ``rand >
+    ratio`` on integers; 0 masks nothing, 1 everything).
+
+    numpy's PCG64 seeded from (seed, rank), like ``ClassMixSampler``; ``get_state`` / ``set_state`` let a
+    resumed run continue the sequence."""
+
+    def __init__(self, seed=1234, rank=0, patch=64, ratio=0.7):
+        self.patch = _check_patch(patch)
+        self.threshold = mask_threshold(ratio)
+        self.ratio = float(ratio)
+        self.rng = np.random.Generator(np.random.PCG64(np.random.SeedSequence([int(seed), int(rank)])))
+
+    def sample(self, n: int, h: int, w: int) -> np.ndarray:
+        """uint32 [n, ceil(h / patch), ceil(w / patch)]: the keys of ``n`` images of ``h`` x ``w`` pixels."""
+        n, h, w = int(n), int(h), int(w)
+        if n < 0 or h < 1 or w < 1:
+            raise ValueError(f"PatchMaskSampler: {n} images of {h} x {w} pixels")
+        return self.rng.integers(0, 1 << 32, size=(n, -(-h // self.patch), -(-w // self.patch)), dtype=np.uint32)
+
+    def get_state(self) -> dict:
+        return self.rng.bit_generator.state
+
+    def set_state(self, state: dict) -> None:
+        self.rng.bit_generator.state = state
+
+
 class EmaTeacher:
     """The mean teacher of a generator on the HIP engine.
 
@@ -391,18 +509,39 @@ class EmaTeacher:
                            return_confidence=True)
 
     def mix(self, images, labels, images_t, sampler, num_classes=19, tau=0.968, ignore_label=255, augment=None,
-            mean=IMG_MEAN):
+            mean=IMG_MEAN, teacher=None):
         """``predict`` on the target batch at the source batch's size, then ``classmix`` with ``sampler``'s keys:
         the ``(mixed_images, mixed_labels, mixed_weights)`` a ``lambda_mix > 0`` batch ends with.  ``augment``: a
         ``StrongAugSampler``; the mixed images then go through ``strong_augment`` with its next draw (labels and
-        weights stay as they are).  ``mean``: what the images had subtracted (B, G, R), for the jitter."""
+        weights stay as they are).  ``mean``: what the images had subtracted (B, G, R), for the jitter.
+        ``teacher``: a ``(pred, conf)`` pair that ``predict`` gave for these target images at this size, used
+        instead of a forward of its own (one teacher forward shared with ``mask``)."""
         n, _, h, w = images.shape
-        pred, conf = self.predict(images_t, (w, h))
+        pred, conf = self.predict(images_t, (w, h)) if teacher is None else teacher
         out = classmix(images, labels, images_t, pred, conf, sampler.sample(n, num_classes), num_classes, tau,
                        ignore_label)
         if augment is None:
             return out
         return (strong_augment(out[0], augment.sample(n, h, w), mean),) + out[1:]
+
+    def mask(self, images_t, sampler, num_classes=19, tau=0.968, ignore_label=255, augment=None, mean=IMG_MEAN,
+             ignore_top=0, ignore_bottom=0, teacher=None):
+        """``predict`` on the target batch at its own size, then ``mask_patches`` with ``sampler``'s (a
+        ``PatchMaskSampler``'s) patch, ratio and next draw: the ``(masked_images, masked_labels, masked_weights)``
+        a ``lambda_mic > 0`` batch ends with.  The teacher labels the whole images; only the student's copy is
+        masked.  ``augment``: a ``StrongAugSampler``; the images go through ``strong_augment`` with its next draw
+        BEFORE the masking (MIC's colour augmentation; the teacher sees the plain images).  ``teacher``: a
+        ``(pred, conf)`` pair to use instead of the forward, as in ``mix``."""
+        if not isinstance(sampler, PatchMaskSampler):
+            raise ValueError(f"EmaTeacher.mask: sampler is {type(sampler).__name__}, expected a PatchMaskSampler")
+        if images_t.dim() != 4:
+            raise RuntimeError(f"EmaTeacher.mask: images_t is {tuple(images_t.shape)}, expected [N, 3, H, W]")
+        n, _, h, w = images_t.shape
+        pred, conf = self.predict(images_t, (w, h)) if teacher is None else teacher
+        if augment is not None:
+            images_t = strong_augment(images_t, augment.sample(n, h, w), mean)
+        return mask_patches(images_t, pred, conf, sampler.sample(n, h, w), sampler.patch, sampler.ratio, num_classes,
+                            tau, ignore_label, ignore_top, ignore_bottom)
 
     # -- checkpoints -----------------------------------------------------------------------------------
     def state_dict(self) -> dict:

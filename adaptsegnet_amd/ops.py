@@ -35,6 +35,9 @@ and, in ``MIX_NAMES``, online self-training (DACS; adaptsegnet_amd/mix.py):
   ema / ema_multi     the mean teacher's update over an arena / a list of small tensors
   classmix_*          ClassMix: per-image statistics, then selection + paste in one launch
   softmax_ce_pw_*     softmax_ce_* with a weight per pixel on the numerator
+and, in ``MIC_NAMES``, masked image consistency (MIC; adaptsegnet_amd/mix.py):
+  conf_count          per image the number of target pixels whose confidence reaches tau
+  patch_mask          patches blanked by the caller's keys, the teacher's labels, the confidence weights
 and, in ``AUG_NAMES``, DACS's strong transform of the mixed images:
   strong_augment      per image a colour jitter, then a Gaussian blur, one launch for the batch
 and, in ``FDA_NAMES``, Fourier Domain Adaptation (adaptsegnet_amd/fda.py):
@@ -207,6 +210,7 @@ def _fake(*args, **kwargs):
 NAMES: list = []        # the ops the engine and the step's own kernels launch
 LOSS_NAMES: list = []   # ops of the optional loss terms around the step (engine=False): never in an engine program
 MIX_NAMES: list = []    # ops of online self-training (adaptsegnet_amd/mix.py, names=MIX_NAMES): likewise
+MIC_NAMES: list = []    # ops of masked image consistency (mix.mask_patches, names=MIC_NAMES): likewise
 AUG_NAMES: list = []    # the mixed images' colour jitter and blur (mix.strong_augment, names=AUG_NAMES): likewise
 FDA_NAMES: list = []    # FDA's spectral transfer and robust entropy term (adaptsegnet_amd/fda.py, names=FDA_NAMES): likewise
 
@@ -964,6 +968,42 @@ def _classmix_apply(images_s, labels_s, images_t, pred_t, count, nconf, keys, ig
         None if mask is None else _pt(mask, torch.uint8, (n, c), f"{what} mask"), _stream()), what)
 
 
+@_op("conf_count(Tensor conf_t, float tau, Tensor(a!) nconf) -> ()", names=MIC_NAMES)
+def _conf_count(conf_t, tau, nconf):
+    """nconf int32 [N] = target pixels with conf >= tau (adaptseg_conf_count): classmix_stats's nconf on its own."""
+    if conf_t.dim() != 3:
+        raise RuntimeError(f"conf_count: conf_t is {tuple(conf_t.shape)}, expected [N, H, W]")
+    n, h, w = conf_t.shape
+    check(_lib.lib().adaptseg_conf_count(
+        n, h, w, _pt(conf_t, torch.float32, (n, h, w), "conf_count conf_t"), float(tau),
+        _pt(nconf, torch.int32, (n,), "conf_count nconf"), _stream()), "conf_count")
+
+
+@_op("patch_mask(Tensor images_t, Tensor pred_t, Tensor nconf, Tensor keys, int patch, int threshold, int num_classes, "
+     "int ignore_label, int ignore_top, int ignore_bottom, Tensor(a!) masked_images, Tensor(b!) labels, "
+     "Tensor(c!) weights) -> ()", names=MIC_NAMES)
+def _patch_mask(images_t, pred_t, nconf, keys, patch, threshold, num_classes, ignore_label, ignore_top, ignore_bottom,
+                masked_images, labels, weights):
+    """keys: the uint32 [N, ceil(H / patch), ceil(W / patch)] random numbers, held in an int32 tensor;
+    threshold = floor(ratio * 2^32), 0 .. 2^32 (adaptseg_patch_mask)."""
+    if images_t.dim() != 4 or images_t.shape[1] != 3:
+        raise RuntimeError(f"patch_mask: images_t is {tuple(images_t.shape)}, expected [N, 3, H, W]")
+    n, _, h, w = images_t.shape
+    patch = int(patch)
+    if patch < 1:
+        raise RuntimeError(f"patch_mask: patch {patch} (expected at least 1)")
+    grid = (n, -(-h // patch), -(-w // patch))
+    what = "patch_mask"
+    check(_lib.lib().adaptseg_patch_mask(
+        n, h, w, patch, int(threshold), int(num_classes), int(ignore_label), int(ignore_top), int(ignore_bottom),
+        _pt(images_t, torch.float32, (n, 3, h, w), f"{what} images_t"),
+        _pt(pred_t, torch.uint8, (n, h, w), f"{what} pred_t"), _pt(nconf, torch.int32, (n,), f"{what} nconf"),
+        _pt(keys, torch.int32, grid, f"{what} keys"),
+        _pt(masked_images, torch.float32, (n, 3, h, w), f"{what} masked_images"),
+        _pt(labels, torch.int64, (n, h, w), f"{what} labels"),
+        _pt(weights, torch.float32, (n, h, w), f"{what} weights"), _stream()), what)
+
+
 @_op("strong_augment(Tensor images, float[] mean, int[] ctl, Tensor table, Tensor(a!) out) -> ()", names=AUG_NAMES)
 def _strong_augment(images, mean, ctl, table, out):
     """Colour jitter, then Gaussian blur, per image (adaptseg_strong_augment).  ``ctl``: the host copy of the
@@ -1036,5 +1076,5 @@ class _Overloads:
 
 
 OPS = _Overloads()
-for _n in NAMES + LOSS_NAMES + MIX_NAMES + AUG_NAMES + FDA_NAMES:
+for _n in NAMES + LOSS_NAMES + MIX_NAMES + MIC_NAMES + AUG_NAMES + FDA_NAMES:
     setattr(OPS, _n, getattr(torch.ops.adaptseg, _n).default)

@@ -31,6 +31,8 @@ two halves of entropy-based adaptation (ADVENT): the discriminators see the weig
 map of a prediction instead of its softmax, and the target branch adds an entropy-minimisation loss.
 ``StepConfig.lambda_mix > 0`` is online self-training (DACS; adaptsegnet_amd/mix.py): a third generator
 forward on a ClassMix image made by a mean teacher, trained with a confidence-weighted cross entropy.
+``StepConfig.lambda_mic > 0`` is masked image consistency (MIC) on top: one more generator forward, on the
+target image with random patches blanked, trained the same way on the teacher's labels of the whole image.
 
 Data parallel (one process per GPU): every rank runs the step on its own shard, and SUM
 all-reduces of the gradient arenas replace DataParallel's gradient gather
@@ -104,6 +106,16 @@ class StepConfig:
     # is plain DACS, its batches (images, labels, mixed_images, mixed_labels, mixed_weights).
     # 0: the step as it was
     lambda_mix: float = 0.0
+    # masked image consistency (MIC, the stage built on DACS; adaptsegnet_amd/mix.py).  With lambda_mic > 0
+    # every batch ends with three more elements after everything else, the mixed triple included:
+    # (masked_images float32 [N, 3, Ht, Wt], masked_labels int64 [N, Ht, Wt], masked_weights float32
+    # [N, Ht, Wt]) at ``input_size_target`` (``EmaTeacher.mask``), and the sub-iteration gains one more
+    # generator forward, on masked_images, upsampled to ``input_size_target``, whose backward is lambda_mic *
+    # cross_entropy2d(pred2, masked_labels, reduction="mean_or_zero", pixel_weight=masked_weights)
+    # (multi-level: + lambda_seg * lambda_mic * the same on pred1).  It runs on the main stream after the
+    # mixed branch if there is one and is then the sub-iteration's last generator backward.  Allowed at every
+    # level: "source-only" batches are (images, labels[, mixed triple], masked triple).  0: the step as it was
+    lambda_mic: float = 0.0
     # run the target-domain generator forward (+ its D forward) on a second HIP stream while
     # the source-domain backward executes (independent: same weights, read-only, separate
     # gradient kernels); the target backward then waits for the source backward.  Results are
@@ -188,6 +200,11 @@ class AdaptSegTrainer:
             raise ValueError(f"lambda_mix {cfg.lambda_mix!r} (expected >= 0)")
         if cfg.lambda_mix > 0 and warper is not None:
             raise ValueError("lambda_mix > 0 with a warper: the mixed image has no flow field of its own "
+                             "(the warper's field belongs to the source image)")
+        if cfg.lambda_mic < 0:
+            raise ValueError(f"lambda_mic {cfg.lambda_mic!r} (expected >= 0)")
+        if cfg.lambda_mic > 0 and warper is not None:
+            raise ValueError("lambda_mic > 0 with a warper: the masked image has no flow field of its own "
                              "(the warper's field belongs to the source image)")
         if cfg.level != "source-only" and model_D2 is None:
             raise ValueError(f"{cfg.level} needs model_D2")
@@ -414,7 +431,8 @@ class AdaptSegTrainer:
     def _step_body(self, i_iter, batches):
         """batches: iterable of ``iter_size`` tuples (images, labels, images_target), or with
         ``cfg.lambda_st > 0`` (images, labels, images_target, labels_target); with
-        ``cfg.lambda_mix > 0`` each ends with (mixed_images, mixed_labels, mixed_weights) besides.
+        ``cfg.lambda_mix > 0`` each ends with (mixed_images, mixed_labels, mixed_weights) besides, and with
+        ``cfg.lambda_mic > 0`` with (masked_images, masked_labels, masked_weights) after that.
 
         Multi-GPU: the generator's gradients are final after its adversarial backward of the
         last sub-iteration, so their all-reduce (the 178 MB arena) is launched right there and
@@ -423,13 +441,12 @@ class AdaptSegTrainer:
         c = self.cfg
         batches = list(batches)
         tsize = self._target_size()
-        nmix = 3 if c.lambda_mix > 0 else 0
+        branches = self._extra_branches()
         if c.lambda_st > 0:   # a malformed self-training batch raises before anything is launched
             for batch in batches:
-                self._st_labels(batch, tsize, nmix)
-        if nmix:              # and so does a malformed mixed triple
-            for batch in batches:
-                self._mix_elements(batch)
+                self._st_labels(batch, tsize, branches)
+        # and so does a malformed mixed or masked triple; each batch's triples are taken apart once, here
+        extras = [self._extra_elements(batch, branches) for batch in batches] if branches else None
         L = StepLosses()
         self.opt.zero_grad()
         for o in (self.opt_D1, self.opt_D2):
@@ -440,16 +457,16 @@ class AdaptSegTrainer:
         self._pending = []
         for idx, batch in enumerate(batches):
             g_done = _GSync(self) if idx == len(batches) - 1 else None
-            mixed = tuple(batch[-3:]) if nmix else None
+            extra = extras[idx] if branches else None
             if c.level == "source-only":
-                self._sub_source_only(batch[0], batch[1], inv, L, g_done, mixed)
+                self._sub_source_only(batch[0], batch[1], inv, L, g_done, extra)
                 continue
             images, labels, images_t = batch[:3]
             labels_t = batch[3] if c.lambda_st > 0 else None
             if c.level == "single-level":
-                self._sub_single(images, labels, images_t, inv, tsize, L, g_done, labels_t, mixed)
+                self._sub_single(images, labels, images_t, inv, tsize, L, g_done, labels_t, extra)
             else:
-                self._sub_multi(images, labels, images_t, inv, tsize, L, g_done, labels_t, mixed)
+                self._sub_multi(images, labels, images_t, inv, tsize, L, g_done, labels_t, extra)
         if not batches:
             self._start_sync((self.model,))
         if batches and c.level != "source-only":
@@ -463,13 +480,28 @@ class AdaptSegTrainer:
                 o.step(grad_scale=gs)
         return L
 
+    def _extra_branches(self):
+        """The branches that follow the target branch, in the order they run and their triples end a batch:
+        (kind, lambda's name, lambda, (W, H) of the triple and of the branch's predictions, that size's name)."""
+        c = self.cfg
+        out = []
+        if c.lambda_mix > 0:
+            out.append(("mixed", "lambda_mix", c.lambda_mix, c.input_size, "input_size"))
+        if c.lambda_mic > 0:
+            out.append(("masked", "lambda_mic", c.lambda_mic, c.input_size_target, "input_size_target"))
+        return out
+
     @staticmethod
-    def _st_labels(batch, tsize, nmix=0):
+    def _triple_names(branches):
+        return ", ".join(f"{b[0]}_images, {b[0]}_labels, {b[0]}_weights" for b in branches)
+
+    @staticmethod
+    def _st_labels(batch, tsize, branches=()):
         """The fourth element of a self-training batch, checked against the target prediction's size
-        (``nmix``: the elements that follow it, the mixed triple of lambda_mix > 0)."""
-        if len(batch) != 4 + nmix:
+        (``branches``: whose triples follow it, lambda_mix's and lambda_mic's)."""
+        if len(batch) != 4 + 3 * len(branches):
             raise ValueError(f"lambda_st > 0: every batch is (images, labels, images_target, labels_target"
-                             f"{', mixed_images, mixed_labels, mixed_weights' if nmix else ''}); "
+                             f"{', ' + AdaptSegTrainer._triple_names(branches) if branches else ''}); "
                              f"got {len(batch)} elements")
         images_t, labels_t = batch[2], batch[3]
         want = (images_t.shape[0], int(tsize[1]), int(tsize[0]))
@@ -478,38 +510,54 @@ class AdaptSegTrainer:
                              f"[N, H, W] at the size the target prediction is upsampled to (W, H) = {tuple(tsize)}")
         return labels_t
 
-    def _mix_elements(self, batch):
-        """The last three elements of a lambda_mix > 0 batch, checked against ``input_size``."""
+    def _extra_elements(self, batch, branches):
+        """The triples a batch ends with, one per branch of ``branches`` (lambda_mix's at ``input_size``, then
+        lambda_mic's at ``input_size_target``), checked: [(branch, (images, labels, weights))]."""
         c = self.cfg
         base = (2 if c.level == "source-only" else 3) + (1 if c.lambda_st > 0 else 0)
-        if len(batch) != base + 3:
-            raise ValueError(f"lambda_mix > 0: every batch ends with (mixed_images, mixed_labels, mixed_weights) "
-                             f"after its {base} other elements; got {len(batch)} elements")
-        images, (mi, ml, mw) = batch[0], batch[-3:]
-        n, (w, h) = images.shape[0], (int(c.input_size[0]), int(c.input_size[1]))
-        for name, t, dtype, want in (("mixed_images", mi, torch.float32, (n, 3, h, w)),
-                                     ("mixed_labels", ml, torch.int64, (n, h, w)),
-                                     ("mixed_weights", mw, torch.float32, (n, h, w))):
-            if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != want:
-                got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
-                raise ValueError(f"{name} is {got}: expected {dtype} {want}, at input_size (W, H) = "
-                                 f"{tuple(c.input_size)}")
-        return mi, ml, mw
+        if len(batch) != base + 3 * len(branches):
+            raise ValueError(f"{', '.join(b[1] for b in branches)} > 0: every batch ends with "
+                             f"({self._triple_names(branches)}) after its {base} other elements; got {len(batch)} "
+                             "elements")
+        out = []
+        for k, branch in enumerate(branches):
+            kind, _, _, size, size_name = branch
+            triple = tuple(batch[base + 3 * k:base + 3 * k + 3])
+            # a masked triple belongs to the target batch, a mixed one (and a source-only one) to the source batch
+            n = batch[2 if kind == "masked" and c.level != "source-only" else 0].shape[0]
+            w, h = int(size[0]), int(size[1])
+            for name, t, dtype, want in ((f"{kind}_images", triple[0], torch.float32, (n, 3, h, w)),
+                                         (f"{kind}_labels", triple[1], torch.int64, (n, h, w)),
+                                         (f"{kind}_weights", triple[2], torch.float32, (n, h, w))):
+                if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != want:
+                    got = f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else type(t).__name__
+                    raise ValueError(f"{name} is {got}: expected {dtype} {want}, at {size_name} (W, H) = "
+                                     f"{tuple(size)}")
+            out.append((branch, triple))
+        return out
 
-    def _sub_mixed(self, mixed, inv, L, g_done):
-        """The mixed branch (lambda_mix > 0): a third generator forward, on the ClassMix image, and the
-        confidence-weighted CE against the mixed labels.  On the main stream, after the target
-        branch's backward and the side stream's join (its BatchNorm running-statistics updates
-        must not race the overlapped target forward); the sub-iteration's last generator backward,
-        so ``g_done`` wraps it.  The discriminator step does not depend on it."""
+    def _sub_extras(self, extras, inv, L, g_done):
+        """The branches after the target branch, in order: the mixed one (lambda_mix > 0), then the masked one
+        (lambda_mic > 0).  The last of them is the sub-iteration's last generator backward: ``g_done`` wraps
+        it, and no branch before it."""
+        for k, (branch, triple) in enumerate(extras):
+            self._sub_extra(branch, triple, inv, L, g_done if k == len(extras) - 1 else None)
+
+    def _sub_extra(self, branch, triple, inv, L, g_done):
+        """One more generator forward, on the ClassMix image (the mixed branch) or on the masked target image
+        (the masked branch), and the confidence-weighted CE against the triple's labels.  On the main stream,
+        after the target branch's backward and the side stream's join (its BatchNorm running-statistics
+        updates must not race the overlapped target forward).  The discriminator step does not depend on it."""
         c = self.cfg
-        mi, ml, mw = mixed
+        kind, _, lam, size, _ = branch
+        tag = "mix" if kind == "mixed" else "mic"
+        mi, ml, mw = triple
         if c.level == "multi-level":
-            pred1, pred2 = self.model(mi, c.input_size)
-            preds, scales, names = [pred2, pred1], [c.lambda_mix * inv, c.lambda_seg * c.lambda_mix * inv], \
-                ["loss_mix2", "loss_mix1"]
+            pred1, pred2 = self.model(mi, size)
+            preds, scales, names = [pred2, pred1], [lam * inv, c.lambda_seg * lam * inv], \
+                [f"loss_{tag}2", f"loss_{tag}1"]
         else:
-            preds, scales, names = [self._pred_single(mi, c.input_size)], [c.lambda_mix * inv], ["loss_mix2"]
+            preds, scales, names = [self._pred_single(mi, size)], [lam * inv], [f"loss_{tag}2"]
         losses = [F.cross_entropy2d(p, ml, c.ignore_label, reduction="mean_or_zero", pixel_weight=mw) for p in preds]
         if g_done is not None:
             g_done.begin()
@@ -541,22 +589,22 @@ class AdaptSegTrainer:
     def _flow(self, images):
         return None if self.warper is None else self.warper(images)[0]
 
-    def _sub_source_only(self, images, labels, inv, L, g_done=None, mixed=None):
+    def _sub_source_only(self, images, labels, inv, L, g_done=None, extras=None):
         """train_gta2cityscapes_multi.py:259-286: warper (if any), segmentation loss on the
         second head, backward; the step is the generator's SGD only."""
         pred2 = self._pred_single(images, self.cfg.input_size, self._flow(images))
         loss_seg2 = F.cross_entropy2d(pred2, labels, self.cfg.ignore_label)
-        last = g_done if mixed is None else None   # with a mixed branch, that is the last generator backward
+        last = g_done if extras is None else None   # else the last mixed / masked branch is the last backward
         if last is not None:
             last.begin()
         self._backward([loss_seg2], [inv])
         L.add("loss_seg2", loss_seg2, inv)
         if last is not None:
             last.end()
-        if mixed is not None:
-            self._sub_mixed(mixed, inv, L, g_done)
+        if extras is not None:
+            self._sub_extras(extras, inv, L, g_done)
 
-    def _sub_single(self, images, labels, images_t, inv, tsize, L, g_done=None, labels_t=None, mixed=None):
+    def _sub_single(self, images, labels, images_t, inv, tsize, L, g_done=None, labels_t=None, extras=None):
         """train_gta2cityscapes_multi.py:385-461."""
         c, D2 = self.cfg, self.D2
         self._set_requires_grad(D2, False)
@@ -585,7 +633,7 @@ class AdaptSegTrainer:
             dev_ = loss_adv_target2.device
             dfork = self._d_fork(dev_)
             self._join_source(ov)
-            last = g_done if mixed is None else None   # with a mixed branch, that is the last generator backward
+            last = g_done if extras is None else None   # else the last mixed / masked branch is the last backward
             if last is not None:
                 last.begin()
             self._backward([loss_adv_target2] + loss_st + loss_ent,
@@ -599,8 +647,8 @@ class AdaptSegTrainer:
             if last is not None:
                 last.end()
         self._overlap_end(ov, pred_target2, loss_adv_target2, *loss_st, *loss_ent, *self._kept(keep2))
-        if mixed is not None:
-            self._sub_mixed(mixed, inv, L, g_done)
+        if extras is not None:
+            self._sub_extras(extras, inv, L, g_done)
 
         self._set_requires_grad(D2, True)
         pred2 = pred2.detach()
@@ -613,7 +661,7 @@ class AdaptSegTrainer:
             self._backward([loss_d2], [inv / 2])
             L.add("loss_D2", loss_d2, inv / 2)
 
-    def _sub_multi(self, images, labels, images_t, inv, tsize, L, g_done=None, labels_t=None, mixed=None):
+    def _sub_multi(self, images, labels, images_t, inv, tsize, L, g_done=None, labels_t=None, extras=None):
         """train_gta2cityscapes_multi.py:578-679."""
         c, D1, D2 = self.cfg, self.D1, self.D2
         self._set_requires_grad(D1, False)
@@ -645,7 +693,7 @@ class AdaptSegTrainer:
             dev_ = loss_adv2.device
             dfork = self._d_fork(dev_)
             self._join_source(ov)
-            last = g_done if mixed is None else None   # with a mixed branch, that is the last generator backward
+            last = g_done if extras is None else None   # else the last mixed / masked branch is the last backward
             if last is not None:
                 last.begin()
             st_scales = [c.lambda_seg * c.lambda_st * inv, c.lambda_st * inv][:len(loss_st)]
@@ -662,8 +710,8 @@ class AdaptSegTrainer:
                 last.end()
         self._overlap_end(ov, pred_target1, pred_target2, loss_adv1, loss_adv2, *loss_st, *loss_ent,
                           *self._kept(keep1, keep2))
-        if mixed is not None:
-            self._sub_mixed(mixed, inv, L, g_done)
+        if extras is not None:
+            self._sub_extras(extras, inv, L, g_done)
 
         self._set_requires_grad(D1, True)
         self._set_requires_grad(D2, True)

@@ -564,6 +564,36 @@ int adaptseg_classmix_apply(int n, int h, int w, int ncls, const float *images_s
 int adaptseg_strong_augment(int n, int h, int w, const float *images_in, const float *mean,
                             const int32_t *ctl_host, const int32_t *ctl, const float *jitter,
                             const float *weights, float *images_out, adaptseg_stream_t stream);
+/* Masked Image Consistency (MIC, Hoyer et al., CVPR 2023), pass 1: nconf[i] = #pixels of target
+   image i with conf_t >= tau (a NaN does not count), int32 [n], conf_t fp32 [n][h][w]: the nconf of
+   adaptseg_classmix_stats without its source-label counts.  Overwritten (cleared on the stream
+   first).  A shuffle reduction per wave, one LDS integer add per wave, one global integer add per
+   block: exact and order-independent.  Rejected on the host (ADAPTSEG_ERR_ARG), here and in pass 2:
+   n, h or w < 1, n > 65535, h * w >= 2^24, a NULL pointer. */
+#define ADAPTSEG_MIC_COUNT_MAX_BLOCKS 512 /* pass 1: blocks per batch, each sweep 256 threads x 4 pixels */
+#define ADAPTSEG_MIC_MAX_BLOCKS 2048      /* pass 2: likewise */
+int adaptseg_conf_count(int n, int h, int w, const float *conf_t, float tau, int32_t *nconf,
+                        adaptseg_stream_t stream);
+/* MIC, pass 2: the student's masked input and the teacher's labels of the WHOLE image.  keys
+   uint32 [n][gh][gw], gh = ceil(h / patch), gw = ceil(w / patch) (the caller's random numbers, one
+   per patch); threshold = floor(ratio * 2^32), an integer in [0, 2^32].  Per pixel (y, x) of image i,
+   with m = (keys[i][y / patch][x / patch] < threshold), compared as integers (threshold 0 masks
+   nothing, 2^32 everything):
+     masked_images[i][:][y][x] = m ? +0.0f : images_t[i][:][y][x]  (fp32 [n][3][h][w], contiguous;
+                                 a kept pixel's bits are copied, NaN payloads included)
+     labels[i][y][x]           = pred_t < num_classes ? pred_t : ignore_label   (int64; not masked)
+     weights[i][y][x]          = (y < ignore_top or y >= h - ignore_bottom) ? 0.0f : q_i,
+                                 q_i = (float)nconf[i] / (float)(h * w)  (one fp32 division)
+   pred_t is the teacher's uint8 class map, nconf pass 1's (or adaptseg_classmix_stats's) counts.
+   16-byte accesses when w % 4 == 0 and every map is 16-byte aligned (pred_t: 4-byte), each pixel of
+   a group of four looking up its own key where patch % 4 != 0; scalar accesses otherwise.  The keys
+   are read through the caches, so a grid of any size is served (patch = 1: h * w keys).  No output
+   may alias an input.  Also rejected: patch < 1, threshold outside [0, 2^32], num_classes outside
+   1..256, ignore_label outside 0..255, a negative ignore_top or ignore_bottom. */
+int adaptseg_patch_mask(int n, int h, int w, int patch, int64_t threshold, int num_classes, int ignore_label,
+                        int ignore_top, int ignore_bottom, const float *images_t, const uint8_t *pred_t,
+                        const int32_t *nconf, const uint32_t *keys, float *masked_images, int64_t *labels,
+                        float *weights, adaptseg_stream_t stream);
 /* FDA spectral transfer (Yang & Soatto, CVPR 2020): image i of src takes the low-frequency
    amplitude spectrum of image i of trg, its phase stays.  src / trg / out fp32 [n][c][h][w];
    the window is |u|, |v| <= b.  With S, T the DFTs of src + mean[ch] and trg + mean[ch]:
