@@ -65,7 +65,8 @@ FUSE_PROB, FUSE_LOGIT = 0, 1
 # adaptseg.h: the grid caps of adaptseg_ema / adaptseg_classmix_* (one sweep = blocks x 256 threads x 4 elements)
 EMA_MAX_BLOCKS, EMA_CHUNK, CLASSMIX_MAX_BLOCKS = 2048, 128, 512
 MIC_COUNT_MAX_BLOCKS, MIC_MAX_BLOCKS = 512, 2048   # adaptseg.h: adaptseg_conf_count's / adaptseg_patch_mask's grid cap, per batch
-BLUR_MAX_RADIUS = 7   # adaptseg.h: the largest blur radius of adaptseg_strong_augment
+RCS_MAX_CANDIDATES = 16   # adaptseg.h: the most candidate windows per sample of adaptseg_crop_class_count
+BLUR_MAX_RADIUS = 7  # adaptseg.h: the largest blur radius of adaptseg_strong_augment
 FDA_MAX_W = 4096      # adaptseg.h: the widest image of adaptseg_fda_transfer (its row twiddles sit in LDS)
 
 
@@ -164,6 +165,11 @@ _SIGS = {
     "adaptseg_classmix_apply": [_I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P],
     "adaptseg_conf_count": [_I, _I, _I, _P, _F, _P, _P],
     "adaptseg_patch_mask": [_I, _I, _I, _I, _L, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "adaptseg_label_class_count": [_I, _I, _I, _P, _P, _I, _P, _P],
+    "adaptseg_crop_class_count_workspace_size": [_I, _I, _I, _I, _I, _I, ctypes.POINTER(ctypes.c_int32),
+                                                 ctypes.POINTER(_SZ)],
+    "adaptseg_crop_class_count": [_I, _I, _I, _I, _I, _I, _P, _P, _P, ctypes.POINTER(ctypes.c_int32), _P, _P, _SZ,
+                                  _P],
     "adaptseg_strong_augment": [_I, _I, _I, _P, ctypes.POINTER(_F), ctypes.POINTER(ctypes.c_int32), _P, _P, _P, _P,
                                 _P],
     "adaptseg_selfinfo_fwd": [_L, _I, _P, _P, _P],

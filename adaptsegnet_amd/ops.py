@@ -43,6 +43,9 @@ and, in ``AUG_NAMES``, DACS's strong transform of the mixed images:
 and, in ``FDA_NAMES``, Fourier Domain Adaptation (adaptsegnet_amd/fda.py):
   fda_transfer        a source batch with the low-frequency amplitude spectrum of a target batch
   entropy_rho_loss_*  entropy_loss_* with FDA's robust penalty ((H / ln C)^2 + eps)^eta per pixel
+and, in ``RCS_NAMES``, rare class sampling (DAFormer's RCS; adaptsegnet_amd/rcs.py):
+  label_class_count   per image the number of pixels of every trainId of a decoded label batch
+  crop_class_count    per sample and candidate window the pixels of the sample's class in the augmented label window
 """
 from __future__ import annotations
 
@@ -213,6 +216,7 @@ MIX_NAMES: list = []    # ops of online self-training (adaptsegnet_amd/mix.py, n
 MIC_NAMES: list = []    # ops of masked image consistency (mix.mask_patches, names=MIC_NAMES): likewise
 AUG_NAMES: list = []    # the mixed images' colour jitter and blur (mix.strong_augment, names=AUG_NAMES): likewise
 FDA_NAMES: list = []    # FDA's spectral transfer and robust entropy term (adaptsegnet_amd/fda.py, names=FDA_NAMES): likewise
+RCS_NAMES: list = []    # rare class sampling's class statistics and crop scores (adaptsegnet_amd/rcs.py, names=RCS_NAMES): likewise
 
 
 def _op(schema, engine=True, names=None):
@@ -1071,10 +1075,55 @@ def _entropy_rho_loss_bwd(x, eta, eps, grad_loss, dx, accumulate):
           "entropy_rho_loss_bwd")
 
 
+# ---- rare class sampling: class statistics and class-aware crops (adaptsegnet_amd/rcs.py) ------------
+def _rcs_labels(labels, what):
+    if labels.dtype != torch.uint8 or labels.dim() != 3 or not labels.is_contiguous():
+        raise RuntimeError(f"{what}: labels are {labels.dtype} {tuple(labels.shape)}, expected a contiguous uint8 "
+                           "[N, H, W]")
+    return labels.shape
+
+
+def _rcs_lut(lut, what):
+    return None if lut is None else _pt(lut, torch.int32, (256,), f"{what} lut")
+
+
+@_op("label_class_count(Tensor labels, Tensor? lut, int num_classes, Tensor(a!) counts) -> ()", names=RCS_NAMES)
+def _label_class_count(labels, lut, num_classes, counts):
+    """counts int64 [N, num_classes] = per image the pixels of every trainId (adaptseg_label_class_count)."""
+    what = "label_class_count"
+    n, h, w = _rcs_labels(labels, what)
+    check(_lib.lib().adaptseg_label_class_count(
+        n, h, w, _p(labels), _rcs_lut(lut, what), int(num_classes),
+        _pi64(counts, (n, int(num_classes)), f"{what} counts"), _stream()), what)
+
+
+@_op("crop_class_count(Tensor labels, Tensor? lut, Tensor classes, int[] params, int crop_h, int crop_w, "
+     "Tensor(a!) counts) -> ()", names=RCS_NAMES)
+def _crop_class_count(labels, lut, classes, params, crop_h, crop_w, counts):
+    """counts int64 [N, K] = the pixels of classes[i] in the label window of every candidate; params: the flattened
+    host array [N][K][5] = (sw, sh, ox, oy, mirror) of include/adaptseg.h (adaptseg_crop_class_count)."""
+    what = "crop_class_count"
+    n, h, w = _rcs_labels(labels, what)
+    if counts.dim() != 2 or counts.shape[0] != n:
+        raise RuntimeError(f"{what}: counts is {tuple(counts.shape)}, expected [{n}, K]")
+    k = counts.shape[1]
+    if len(params) != 5 * n * k:
+        raise RuntimeError(f"{what}: expected {5 * n * k} params for {n} samples x {k} candidates, got {len(params)}")
+    pa = (ctypes.c_int32 * (5 * n * k))(*params)
+    b = ctypes.c_size_t(0)
+    check(_lib.lib().adaptseg_crop_class_count_workspace_size(n, h, w, int(crop_h), int(crop_w), k, pa,
+                                                              ctypes.byref(b)), "crop_class_count_workspace_size")
+    wp, wsz = _ws_args(b.value, labels.device)
+    check(_lib.lib().adaptseg_crop_class_count(
+        n, h, w, int(crop_h), int(crop_w), k, _p(labels), _rcs_lut(lut, what),
+        _pt(classes, torch.int32, (n,), f"{what} classes"), pa, _pi64(counts, (n, k), f"{what} counts"), wp, wsz,
+        _stream()), what)
+
+
 class _Overloads:
     """torch.ops.adaptseg.<name>.default for every op (skips the packet's overload lookup)."""
 
 
 OPS = _Overloads()
-for _n in NAMES + LOSS_NAMES + MIX_NAMES + MIC_NAMES + AUG_NAMES + FDA_NAMES:
+for _n in NAMES + LOSS_NAMES + MIX_NAMES + MIC_NAMES + AUG_NAMES + FDA_NAMES + RCS_NAMES:
     setattr(OPS, _n, getattr(torch.ops.adaptseg, _n).default)

@@ -594,6 +594,47 @@ int adaptseg_patch_mask(int n, int h, int w, int patch, int64_t threshold, int n
                         int ignore_top, int ignore_bottom, const float *images_t, const uint8_t *pred_t,
                         const int32_t *nconf, const uint32_t *keys, float *masked_images, int64_t *labels,
                         float *weights, adaptseg_stream_t stream);
+/* Rare class sampling (RCS; Hoyer et al., DAFormer, CVPR 2022, section 3.2), the class statistics:
+   counts[i][c] = the number of pixels of image i whose trainId is c, for c in [0, num_classes); int64
+   [n][num_classes], OVERWRITTEN (this entry point clears it on the stream, then launches the kernel
+   that adds into it).  ids uint8 [n][h][w], the decoded label files at their own size; lut int32
+   [256] id -> trainId (data.trainid_lut's table), or NULL for ids that are trainIds already.  An id
+   that maps outside [0, num_classes) counts nowhere.  Per-block LDS bins with a wave-level combine,
+   one 64-bit integer atomic per non-zero bin: exact and order-independent.  16-byte loads where
+   h * w % 16 == 0 and ids is 16-byte aligned (every w % 16 == 0), one byte per lane otherwise.
+   Rejected on the host before any launch (ADAPTSEG_ERR_ARG): n, h or w < 1, n > 65535,
+   h * w >= 2^31, num_classes outside 1..255, a NULL ids or counts. */
+int adaptseg_label_class_count(int n, int h, int w, const uint8_t *ids, const int32_t *lut, int num_classes,
+                               int64_t *counts, adaptseg_stream_t stream);
+/* RCS, the class-aware crop: counts[i][k] = the number of pixels equal to classes[i] in the label
+   window that adaptseg_gta5_preprocess_augment returns for sample i under params[i][k], for K
+   candidate parameter sets per sample, bit-exact for every valid set (down- and upscaling, mirror,
+   windows partly or wholly outside the scaled image; padding counts for no class).  No image is
+   resized and no window materialised: the label window is separable, so the count is
+   sum_sy sum_sx my[sy] mx[sx] [lut[ids[sy][sx]] == class] with mx / my the number of window columns /
+   rows that read a source column / row, and ONE read of the label rows scores all K candidates.
+   ids uint8 [n][in_h][in_w]; lut as above; classes DEVICE int32 [n]; params HOST int32 [n][K][5] =
+   (sw, sh, ox, oy, mirror), preprocess_augment's parameters; counts DEVICE int64 [n][K],
+   overwritten; (cw, ch) the window.  Two kinds of launch on the caller's stream, no host sync:
+     prepare  per sample, walks every candidate's nearest coordinates exactly as preprocess_augment
+              does (sequential double accumulation, contraction off), stores the multiplicities,
+              packs the column multiplicities into bit planes, lists the ids of the sample's class,
+              records the union of the columns and the hull of the rows the candidates read, and
+              clears counts
+     count    a wave per label row, 16-byte aligned loads whatever the row's own alignment; rows no
+              candidate reads and columns outside the union are skipped; up to 16 accumulators in
+              registers; one 64-bit integer atomic per block and candidate
+   The workspace (adaptseg_crop_class_count_workspace_size; 16-byte aligned) holds the tables only.
+   Rejected on the host before any launch: preprocess_augment's checks with its limits (sw, sh
+   outside [1, 2^20), |ox| or |oy| >= 2^20, mirror not 0 / 1, a downscale factor above 15, a crop
+   side >= 2^20), K outside 1..ADAPTSEG_RCS_MAX_CANDIDATES, ch * cw >= 2^31, in_h * in_w >= 2^31,
+   n > 65535, a NULL pointer, a NULL or short workspace (ADAPTSEG_ERR_WORKSPACE). */
+#define ADAPTSEG_RCS_MAX_CANDIDATES 16
+int adaptseg_crop_class_count_workspace_size(int n, int in_h, int in_w, int ch, int cw, int K,
+                                             const int32_t *params, size_t *bytes);
+int adaptseg_crop_class_count(int n, int in_h, int in_w, int ch, int cw, int K, const uint8_t *ids,
+                              const int32_t *lut, const int32_t *classes, const int32_t *params, int64_t *counts,
+                              void *workspace, size_t ws_bytes, adaptseg_stream_t stream);
 /* FDA spectral transfer (Yang & Soatto, CVPR 2020): image i of src takes the low-frequency
    amplitude spectrum of image i of trg, its phase stays.  src / trg / out fp32 [n][c][h][w];
    the window is |u|, |v| <= b.  With S, T the DFTs of src + mean[ch] and trg + mean[ch]:
